@@ -17,7 +17,7 @@ of the same aggregate is split into N contiguous 64-element-aligned slices
 (dlsim_shard_range), rank r reduces slice r of all N models with no data-path
 collective. `value` = the config's bytes x K / the max over ranks of each
 rank's HIP-event time around its K launches; the barriers that line the ranks
-up sit outside that window. The line carries the speed-up over the same
+up sit outside that window. With --full the line carries the speed-up over the same
 config on one GPU (rank 0 times it alone, same K, same timing) and, in their
 own fields, the RCCL all-gather that would materialise the full output and
 the C ABI's sharded entry points (local reduce + grouped in-place broadcasts
@@ -29,6 +29,14 @@ write 1). Input sets rotate, with enough sets that their footprint is >= 1 GiB,
 so the 256 MiB Infinity Cache cannot serve re-reads (small slices included).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes the aggregate the last timed step produced
+(DIR/aggregate.npy, float32; DIR/aggregate_rank<r>.npy for N > 1). --full adds
+what takes runs of its own: the CPU baseline, the launch floor, the committed
+PMC traffic of the roofline and, for N > 1, the gathers, the sharded C ABI and
+the one-GPU reference of the speed-up.
 """
 from __future__ import annotations
 
@@ -139,6 +147,13 @@ def parse(argv=None):
                     help="N > 1: skip rank 0's timing of the whole config alone (the speed-up base)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="budget for the CPU baseline sample (rank 0, N=1 only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the aggregate of the last timed step as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of it beyond 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the launch floor, the "
+                         "roofline's committed PMC traffic and, for N > 1, the gathers, the sharded C ABI and the "
+                         "one-GPU reference (default: only the timed steps and the result line)")
     return ap.parse_args(argv)
 
 
@@ -276,7 +291,7 @@ class ReduceWorkload:
         # outputs as the product allocates aggregate outputs (arena_empty)
         p_pad = row_stride(p, esz)
         al = base_align(p * esz, esz)
-        self.plans, self.probe_plans, self.outs, self._keep = [], [], [], []
+        self.plans, self.probe_plans, self.outs, self.results, self._keep = [], [], [], [], []
         # every set's rows in ONE allocation, as the staging buffer holds a
         # call's rows, and allocated as the staging is (arena.resident_empty:
         # physically contiguous from 64 MiB on): rows in separate per-set
@@ -312,6 +327,7 @@ class ReduceWorkload:
                 plan = _native.ReducePlan([x[i, :p] for i in range(n)], w32, out, mode)
                 assert all(t.data_ptr() % 16 == 0 for t in plan._keep[0]), "arena rows must be 16-B aligned"
                 self.outs.append(out)
+                self.results.append(out)
                 if j < self.sets:
                     self.probe_plans.append(_native.ReducePlan([x[i, :p] for i in range(n)], w32, out, mode,
                                                                probe=True))
@@ -320,6 +336,7 @@ class ReduceWorkload:
                 plan = _native.BatchPlan([([x[b, i, :p] for i in range(n)], w32, ob[b, :p]) for b in range(batch)],
                                          mode)
                 self.outs.append(ob[0, :p])
+                self.results.append(ob[:, :p])
                 self._keep.append(ob)
             self.plans.append(plan)
         self.kernel = _native.kernel_name(n, p, tdt, mode) if batch == 1 else "dlsim::k_wreduce_batch_table"
@@ -354,6 +371,11 @@ class ReduceWorkload:
 
     def launch(self, k):
         self.plans[k % self.out_sets].launch(self.stream)
+
+    def result(self, k):
+        """What step k's launch produced: the aggregate (batch 1) or the
+        batch's aggregates as rows."""
+        return self.results[k % self.out_sets]
 
     def launch_probe(self, k):
         self.probe_plans[k % len(self.probe_plans)].launch(self.stream)
@@ -573,6 +595,42 @@ def cpu_baseline(config, n, p, dtype, weights, budget_s):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20  # all ranks' dumped arrays together
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_sample_index(numel: int, max_elems: int):
+    """Which elements of a numel-element output the dump keeps: all of them
+    (None) if they fit, else max_elems sorted indices drawn once from a fixed
+    seed, the same for every run and build."""
+    if numel <= max_elems:
+        return None
+    idx = np.random.default_rng(DUMP_SAMPLE_SEED).choice(numel, size=max_elems, replace=False)
+    idx.sort()
+    return idx
+
+
+def dump_outputs(directory: str, wl, last_step: int, rank: int, world: int, sync) -> dict:
+    """Write what the last timed step's launch produced (the aggregate a caller
+    of the path receives; a batch's aggregates as rows) as float32 .npy, every
+    stored value exactly (f32 as is, bf16/f16 widened). Returns what was
+    written, for the result line."""
+    sync()
+    os.makedirs(directory, exist_ok=True)
+    out = wl.result(last_step)
+    flat = out.reshape(-1)
+    idx = dump_sample_index(flat.numel(), DUMP_MAX_BYTES // 4 // world)
+    if idx is not None:
+        flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+    arr = flat.to(torch.float32).cpu().numpy()
+    if idx is None:
+        arr = arr.reshape(tuple(out.shape))
+    name = "aggregate" if world == 1 else f"aggregate_rank{rank}"
+    np.save(os.path.join(directory, name + ".npy"), arr)
+    return {"file": name + ".npy", "step": last_step, "shape": list(arr.shape), "dtype": "float32",
+            "of_elements": out.numel(), "sampled": idx is not None}
+
+
 # ---- one rank -------------------------------------------------------------------
 
 def run_rank(args, rank: int, world: int, local: int):
@@ -625,6 +683,7 @@ def run_rank(args, rank: int, world: int, local: int):
         wl.launch(k)
     K = args.steps
     ev_ms, wall_ms = time_steps(wl.launch, K, sync, barrier, new_event)
+    dumped = dump_outputs(args.dump_outputs, wl, K - 1, rank, world, sync) if args.dump_outputs else None
 
     stats = torch.tensor([ev_ms, wall_ms, float(wl.bytes_per_step) * K], dtype=torch.float64, device=cdev)
     per_rank_us = torch.tensor([ev_ms / K * 1e3], dtype=torch.float64, device=cdev)
@@ -644,12 +703,12 @@ def run_rank(args, rank: int, world: int, local: int):
 
     # ---- N > 1: the output all-gather, in its own fields -----------------------
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         gather = _time_gathers(args, wl, rank, world, p_cfg, p, n, w32, mode, dtype, dev, cdev, stream, strong, barrier)
 
     # ---- N > 1 strong: the same config on one GPU (rank 0 alone) ----------------
     single = None
-    if strong and not args.no_single_gpu_reference:
+    if strong and args.full and not args.no_single_gpu_reference:
         barrier()
         if rank == 0:
             full = ReduceWorkload(n, p_cfg, dtype, w32, mode, B, dev, 99, stream)
@@ -666,11 +725,15 @@ def run_rank(args, rank: int, world: int, local: int):
     result = None
     if rank == 0:
         achieved = wl.bytes_per_step / (ev_ms / K * 1e-3) / 1e9
-        traffic, traffic_src = (pmc_traffic(args.config, args.mode, split) if B == 1
-                                else (None, "no committed PMC summary for batched launches"))
+        if not args.full:
+            traffic, traffic_src = None, "looked up with --full only"
+        elif B == 1:
+            traffic, traffic_src = pmc_traffic(args.config, args.mode, split)
+        else:
+            traffic, traffic_src = None, "no committed PMC summary for batched launches"
         probe = xor_probe(wl, K, sync, new_event, achieved) if B == 1 and args.xor_probe else None
         floor = launch_floor(wl, n, dtype, w32, mode, dev, K, sync, new_event, ev_ms / K * 1e3) \
-            if B == 1 else None
+            if B == 1 and args.full else None
         # opt-in: its concurrent launches share the reduce's kernel name, so
         # they would skew rocprof's per-dispatch average of the same command
         overlap = two_streams(wl, K, sync, dev) if B == 1 and args.two_streams else None
@@ -720,6 +783,8 @@ def run_rank(args, rank: int, world: int, local: int):
             "launch_floor": floor,
             "two_streams": overlap,
         }
+        if dumped:
+            result["dumped_outputs"] = dumped
         if probe:
             result["xor_probe"] = probe
         if single:
@@ -728,11 +793,11 @@ def run_rank(args, rank: int, world: int, local: int):
             result["allgather"] = gather
     barrier()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.config, n, p, dtype, weights, args.cpu_seconds)
         else:
             result["cpu_baseline"] = None
-    if world > 1 and args.backend == "nccl" and strong:
+    if world > 1 and args.backend == "nccl" and strong and args.full:
         # last, and under a watchdog: RCCL calls made by the library itself
         def on_timeout():
             if rank == 0:

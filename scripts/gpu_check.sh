@@ -12,6 +12,6 @@ rc=$?; tail -25 $O/pytest_gpu.log | grep -vE "^\s*$" | tail -12
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 step smoke;  timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 tail -1 $O/smoke.log
-step bench;  timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err || exit $?
+step bench;  timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 cat $O/bench.json
 step done

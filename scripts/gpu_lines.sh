@@ -16,14 +16,14 @@ if [ "${2:-}" = "--suite" ]; then
   step smoke; timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
   tail -1 $O/smoke.log
 fi
-step bench default; timeout -k 10 300 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit $?
+step bench default; timeout -k 10 300 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit $?
 for i in 1 2; do
-  timeout -k 10 120 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_$i.json 2> $O/bench_driver_$i.err || exit $?
+  timeout -k 10 120 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_$i.json 2> $O/bench_driver_$i.err || exit $?
 done
 for spec in cfg2:1 cfg3:1 cfg4:1 cfg5:1 north_star:2 north_star:4 north_star:8 cfg3:8 cfg5:8 cfg4:4; do
   IFS=: read -r C S <<< "$spec"
   step "bench $C slice $S"
-  timeout -k 10 300 python3 bench.py --config $C --slice-of $S --no-cpu-baseline > $O/bench_${C}_s$S.json 2> $O/bench_${C}_s$S.err || exit $?
+  timeout -k 10 300 python3 bench.py --full --config $C --slice-of $S --no-cpu-baseline > $O/bench_${C}_s$S.json 2> $O/bench_${C}_s$S.err || exit $?
 done
 python3 - "$O" <<'PY'
 import glob, json, os, sys

@@ -21,7 +21,7 @@ n, p, dt, _, _ = bench.CONFIGS['$C']
 b, e = _native.shard_range(p, $S, 0, 64)
 print((n + 1) * (e - b) * bench.ELEM_BYTES[dt])")
   local ARGS="--config $C --slice-of $S --no-cpu-baseline"
-  step "$NAME bench";  timeout -k 10 300 python3 bench.py $ARGS > $O/bench_$NAME.json 2> $O/bench_$NAME.err || return 1
+  step "$NAME bench";  timeout -k 10 300 python3 bench.py --full $ARGS > $O/bench_$NAME.json 2> $O/bench_$NAME.err || return 1
   step "$NAME trace";  timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace_$NAME -o run -- python3 $R/bench.py $ARGS --steps 200 --warmup 20 > $O/trace_$NAME.log 2>&1 || return 1
   step "$NAME fetch";  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -f csv -d $O/fetch_$NAME -o run -- python3 $R/bench.py $ARGS --steps 50 --warmup 5 > $O/fetch_$NAME.log 2>&1 || return 1
   step "$NAME write";  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -f csv -d $O/write_$NAME -o run -- python3 $R/bench.py $ARGS --steps 50 --warmup 5 > $O/write_$NAME.log 2>&1 || return 1

@@ -15,7 +15,7 @@ step() { echo "[$(date +%T)] $*"; }
 run() {  # name, bench.py arguments
   local NAME=$1; shift
   step "$NAME: bench.py $*"
-  timeout -k 10 400 python3 bench.py "$@" > $O/$NAME.json 2> $O/$NAME.err
+  timeout -k 10 400 python3 bench.py --full "$@" > $O/$NAME.json 2> $O/$NAME.err
   local rc=$?
   if [ $rc -ne 0 ]; then echo "rc=$rc for $NAME"; tail -30 $O/$NAME.err; exit $rc; fi
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['n_gpus'], d['value'], d['timing']['kernel_avg_us_per_rank'])" $O/$NAME.json || exit 1
@@ -28,7 +28,7 @@ run g4_north_star --gpus 4 --backend gloo --steps 20 --warmup 5
 # the driver's own launcher (torchrun sets RANK/WORLD_SIZE; bench.py does not spawn)
 step "torchrun g4"
 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 4 --backend gloo --steps 20 --warmup 5 > $O/torchrun_g4.json 2> $O/torchrun_g4.err \
+  --master-port 29517 bench.py --full --gpus 4 --backend gloo --steps 20 --warmup 5 > $O/torchrun_g4.json 2> $O/torchrun_g4.err \
   || { echo "torchrun rc=$?"; tail -30 $O/torchrun_g4.err; exit 1; }
 python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['n_gpus'], d['value'])" $O/torchrun_g4.json || exit 1
 # rank 0's 8-rank slice alone, traced: K = 200 timed launches after 20 warm-ups

@@ -13,7 +13,7 @@ for leg in on off; do
     if [ $cfg = s8 ]; then extra="--slice-of 8"; sets=22; else extra=""; sets=3; fi
     if [ $leg = off ]; then export DLSIM_BENCH_PRIME=0; prime=0; else unset DLSIM_BENCH_PRIME; prime=8; fi
     timeout -k 10 240 rocprofv3 --kernel-trace -d "$OUT/${cfg}_${leg}" -o run --output-format csv -- \
-      python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline $extra > "$OUT/${cfg}_${leg}.json" 2> "$OUT/${cfg}_${leg}.err"
+      python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline $extra > "$OUT/${cfg}_${leg}.json" 2> "$OUT/${cfg}_${leg}.err"
     python3 scripts/dispatch_buckets.py "$(find "$OUT/${cfg}_${leg}" -name '*kernel_trace.csv')" --sets $sets \
       --warmup 20 --steps 200 --prime $prime --kernel k_wreduce --out "$OUT/${cfg}_${leg}_buckets.json" > /dev/null
     python3 - "$OUT/${cfg}_${leg}" <<'PY'

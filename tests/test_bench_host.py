@@ -57,6 +57,24 @@ def test_strong_split_is_the_default_for_several_gpus():
     assert bench.parse(["--gpus", "4", "--weak"]).weak
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full and a.dump_outputs == "somewhere"
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    import numpy as np
+    assert bench.dump_sample_index(1000, 1000) is None
+    idx = bench.dump_sample_index(100_000, 1000)
+    assert idx.shape == (1000,) and len(np.unique(idx)) == 1000
+    assert idx.min() >= 0 and idx.max() < 100_000 and (np.diff(idx) > 0).all()
+    assert (idx == bench.dump_sample_index(100_000, 1000)).all()
+    # the largest config's output (125 M elements) keeps 64 MB of float32
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+
+
 _RANK_SCRIPT = textwrap.dedent("""
     import json, os, sys
     import torch, torch.distributed as dist
