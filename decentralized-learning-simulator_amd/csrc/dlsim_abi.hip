@@ -194,6 +194,39 @@ int device_cus() {
   return c;
 }
 
+// The fresh-SGD step's dispatch (inst_sgd.hip): arguments already checked.
+hipError_t sgd_flat(const void* p, const void* g, void* out, size_t nelem, double lr, double wd, int dtype,
+                    hipStream_t st);
+hipError_t sgd_tensors(int t, const void* const* p, const void* const* g, void* const* out, const size_t* nelem,
+                       double lr, double wd, int dtype, hipStream_t st);
+
+// dtype and hyper-parameters of dlsim_sgd_step / dlsim_sgd_step_tensors
+int check_sgd_scalars(double lr, double wd, int dtype) {
+  if (dtype == DLSIM_F16)
+    return fail(DLSIM_E_DTYPE, "DLSIM_F16 has no SGD-step kernel (PyTorch's CPU result depends on its thread "
+                               "count; run torch's own add sequence)");
+  if (dtype != DLSIM_F32 && dtype != DLSIM_BF16 && dtype != DLSIM_F64)
+    return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  if (!(lr >= 0.0)) return fail(DLSIM_E_ARG, "lr must be >= 0 (got %g)", lr);
+  if (!(wd >= 0.0)) return fail(DLSIM_E_ARG, "weight_decay must be >= 0 (got %g)", wd);
+  return DLSIM_OK;
+}
+
+// One (param, grad, out) triple: the output may BE the parameter or the
+// gradient (a lane reads both terms of an element before writing it); any
+// other overlap is rejected.
+int check_sgd_buffers(const void* p, const void* g, const void* out, size_t nelem, size_t esz) {
+  if (nelem == 0) return DLSIM_OK;
+  if (!p || !g || !out) return fail(DLSIM_E_ARG, "null parameter, gradient or output pointer");
+  const size_t bytes = nelem * esz;
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + bytes;
+  const uintptr_t ins[2] = {reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(g)};
+  for (int i = 0; i < 2; ++i)
+    if (ins[i] != o0 && ins[i] < o1 && o0 < ins[i] + bytes)
+      return fail(DLSIM_E_ARG, "output partially overlaps the %s", i == 0 ? "parameter" : "gradient");
+  return DLSIM_OK;
+}
+
 }  // namespace dlsim_host
 
 // the per-policy entries live in the inst_*.hip units
@@ -897,6 +930,47 @@ int dlsim_wreduce_mixed(const void* const* d_inputs, const int* dtypes, int n, c
     if (e != hipSuccess) return hip_fail(e, "k_wreduce_mixed launch");
   }
   return DLSIM_OK;
+}
+
+int dlsim_sgd_step(const void* d_param, const void* d_grad, void* d_out, size_t n_elems, double lr,
+                   double weight_decay, int dtype, void* stream) {
+  g_err.clear();
+  int rc = check_sgd_scalars(lr, weight_decay, dtype);
+  if (rc == DLSIM_OK) rc = check_sgd_buffers(d_param, d_grad, d_out, n_elems, elem_bytes(dtype));
+  if (rc != DLSIM_OK || n_elems == 0) return rc;
+  const hipError_t e = sgd_flat(d_param, d_grad, d_out, n_elems, lr, weight_decay, dtype,
+                                static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "SGD step launch");
+}
+
+int dlsim_sgd_step_tensors(int t, const void* const* d_params, const void* const* d_grads, void* const* d_outs,
+                           const size_t* numels, double lr, double weight_decay, int dtype, void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_sgd_scalars(lr, weight_decay, dtype);
+  if (rc != DLSIM_OK || t == 0) return rc;
+  if (!d_params || !d_grads || !d_outs || !numels) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  std::vector<const void*> ins(static_cast<size_t>(t) * 2);
+  for (int k = 0; k < t; ++k) {
+    rc = check_sgd_buffers(d_params[k], d_grads[k], d_outs[k], numels[k], esz);
+    if (rc != DLSIM_OK) return fail(rc, "tensor %d: %s", k, std::string(g_err).c_str());
+    ins[static_cast<size_t>(k) * 2] = d_params[k];
+    ins[static_cast<size_t>(k) * 2 + 1] = d_grads[k];
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // One grid runs the tensors concurrently; t calls run them in order. They
+  // differ only if a tensor's output shares bytes with another tensor's
+  // buffers: such lists go as t launches, in order.
+  const std::vector<int> fan(static_cast<size_t>(t), 2);
+  hipError_t e = hipSuccess;
+  if (cross_task_overlap(t, fan.data(), ins.data(), d_outs, numels, esz)) {
+    for (int k = 0; k < t && e == hipSuccess; ++k)
+      if (numels[k]) e = sgd_flat(d_params[k], d_grads[k], d_outs[k], numels[k], lr, weight_decay, dtype, st);
+  } else {
+    e = sgd_tensors(t, d_params, d_grads, d_outs, numels, lr, weight_decay, dtype, st);
+  }
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "SGD step launch");
 }
 
 int dlsim_device_alloc(size_t nbytes, int flags, void** d_out, int* contiguous) {

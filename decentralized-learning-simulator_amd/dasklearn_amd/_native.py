@@ -57,6 +57,8 @@ EXPORTS = (
     "dlsim_wreduce_sharded",
     "dlsim_wreduce_sharded_f64",
     "dlsim_wreduce_mixed",
+    "dlsim_sgd_step",
+    "dlsim_sgd_step_tensors",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -176,6 +178,11 @@ def load() -> ctypes.CDLL:
         lib.dlsim_wreduce_mixed.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i), i, ctypes.POINTER(ctypes.c_double),
                                             vp, i, sz, vp]
         lib.dlsim_wreduce_mixed.restype = i
+        lib.dlsim_sgd_step.argtypes = [vp, vp, vp, sz, ctypes.c_double, ctypes.c_double, i, vp]
+        lib.dlsim_sgd_step.restype = i
+        lib.dlsim_sgd_step_tensors.argtypes = [i, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                               ctypes.POINTER(sz), ctypes.c_double, ctypes.c_double, i, vp]
+        lib.dlsim_sgd_step_tensors.restype = i
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -344,6 +351,61 @@ def wreduce_mixed(inputs, weights, out, stream=None):
            load().dlsim_wreduce_mixed(ptrs, codes, n, w, out.data_ptr(), dtype_code(out.dtype, single_task=True),
                                       numel, _stream_handle(out.device, stream)))
     return out
+
+
+def sgd_kernel_dtype(torch_dtype) -> bool:
+    """Whether dlsim_sgd_step has a kernel for this dtype (fp32, bf16, fp64;
+    fp16 runs torch's own CPU ops, dasklearn_amd/sgd.py)."""
+    import torch
+    return torch_dtype in (torch.float32, torch.bfloat16, torch.float64)
+
+
+def _check_sgd_triple(p, g, out) -> None:
+    for t in (p, g, out):
+        if not t.is_cuda or t.device != out.device:
+            raise ValueError("the SGD step needs device tensors on one device (no CPU path)")
+        if t.dtype != out.dtype or t.numel() != out.numel() or not t.is_contiguous():
+            raise ValueError("parameter, gradient and output must be contiguous, same dtype and size")
+
+
+def sgd_step(param, grad, out, lr: float, weight_decay: float, stream=None):
+    """dlsim_sgd_step: out = the first step of a fresh torch.optim.SGD(lr,
+    weight_decay) on `param` with gradient `grad` (flat device tensors; `out`
+    may be `param` or `grad`), stream-ordered."""
+    _check_sgd_triple(param, grad, out)
+    _check("dlsim_sgd_step",
+           load().dlsim_sgd_step(param.data_ptr(), grad.data_ptr(), out.data_ptr(), out.numel(), float(lr),
+                                 float(weight_decay), dtype_code(out.dtype, single_task=True),
+                                 _stream_handle(out.device, stream)))
+    return out
+
+
+def sgd_step_tensors_raw(param_ptrs: Sequence[int], grad_ptrs: Sequence[int], out_ptrs: Sequence[int],
+                         numels: Sequence[int], lr: float, weight_decay: float, dtype: int, stream_handle) -> None:
+    """dlsim_sgd_step_tensors on raw device pointers (the caller checked them)."""
+    t = len(numels)
+    arr = ctypes.c_void_p * max(t, 1)
+    _check("dlsim_sgd_step_tensors",
+           load().dlsim_sgd_step_tensors(t, arr(*param_ptrs), arr(*grad_ptrs), arr(*out_ptrs),
+                                         (ctypes.c_size_t * max(t, 1))(*numels), float(lr), float(weight_decay),
+                                         dtype, stream_handle))
+
+
+def sgd_step_tensors(params, grads, outs, lr: float, weight_decay: float, stream=None):
+    """dlsim_sgd_step_tensors: the same step over separate (param, grad, out)
+    device tensors of one dtype, in a few launches."""
+    if not (len(params) == len(grads) == len(outs)):
+        raise ValueError("params, grads and outs must have one length")
+    if not outs:
+        return outs
+    for p, g, o in zip(params, grads, outs):
+        _check_sgd_triple(p, g, o)
+        if o.dtype != outs[0].dtype or o.device != outs[0].device:
+            raise ValueError("one call takes tensors of one dtype on one device")
+    sgd_step_tensors_raw([p.data_ptr() for p in params], [g.data_ptr() for g in grads],
+                         [o.data_ptr() for o in outs], [o.numel() for o in outs], lr, weight_decay,
+                         dtype_code(outs[0].dtype, single_task=True), _stream_handle(outs[0].device, stream))
+    return outs
 
 
 DLSIM_ALLOC_CONTIGUOUS = 1

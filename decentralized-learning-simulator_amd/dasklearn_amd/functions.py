@@ -1,4 +1,6 @@
-"""The `aggregate` compute task — drop-in for dasklearn/functions.py:89-106.
+"""The worker's parameter-arithmetic tasks. `aggregate` is the drop-in for
+dasklearn/functions.py:89-106; `gradient_update` (functions.py:85-86), `chunk`
+and `reconstruct_from_chunks` (functions.py:136-146) follow below.
 
 `dasklearn/worker.py:27-31` resolves task functions with
 `globals()[func_name]` over `from dasklearn.functions import *`; exporting an
@@ -19,7 +21,7 @@ from dasklearn_amd.model_manager import ModelManager
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["aggregate", "chunk", "reconstruct_from_chunks"]
+__all__ = ["aggregate", "gradient_update", "chunk", "reconstruct_from_chunks"]
 
 # The reference builds the model to reconstruct into from its model zoo
 # (functions.py:144, dasklearn.models.create_model). Out of scope here, so it
@@ -58,6 +60,21 @@ def aggregate(settings, params: Dict) -> List[nn.Module]:
     agg_model = model_manager.aggregate_trained_models(weights)
     logger.debug("Model aggregation took %f s.", time.time() - start_time)
     return [agg_model]
+
+
+def gradient_update(settings, params: Dict) -> List[nn.Module]:
+    """functions.py:85-86 -> ModelTrainer.gradient_update (model_trainer.py:133-143):
+    the first step of a fresh SGD(settings.learning.{learning_rate, momentum,
+    weight_decay}) on params["model"] with params["gradient_model"].gradient,
+    on the GPU; needs no dataset. The input model is only read (the reference
+    updates it in place): the returned model alone carries the update."""
+    from dasklearn_amd.sgd import sgd_step_module
+    model = params["model"]
+    if isinstance(model, tuple):  # the first round's (model, 0), functions.py:31-32
+        model = model[0]
+    learning = settings.learning
+    return [sgd_step_module(model, params["gradient_model"].gradient, learning.learning_rate, learning.momentum,
+                            learning.weight_decay)]
 
 
 def chunk(settings, params: Dict) -> List:

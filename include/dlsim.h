@@ -509,6 +509,52 @@ int dlsim_wreduce_mixed(const void* const* d_inputs, const int* dtypes, int n, c
                         void* d_out, int out_dtype, size_t n_elems, void* stream);
 
 /*
+ * dlsim_sgd_step: the first step of a fresh torch.optim.SGD on one flat
+ * buffer, the arithmetic of the `gradient_update` task:
+ *   dasklearn/functions.py:85-86           gradient_update(settings, params)
+ *   dasklearn/model_trainer.py:133-143     ModelTrainer.gradient_update: a new
+ *                                          SGD(lr, momentum, weight_decay),
+ *                                          param.grad = grad, one step()
+ * A fresh optimizer's momentum buffer is a clone of the gradient, so momentum
+ * takes no part. Per element, as torch's CPU ops round it:
+ *   g' = grad + weight_decay * param      (skipped when weight_decay == 0, so
+ *                                          an infinite parameter stays infinite)
+ *   d_out = param - lr * g'
+ * each line ONE fused multiply-add with the scalar rounded to the element
+ * type first: fp32: fma(f32(wd), p, g), fma(-f32(lr), g', p); fp64: double fma,
+ * exact scalars; bf16: scalars rounded to bf16 (through fp32), each line in
+ * fp32 and its result rounded to bf16, except the elements PyTorch's scalar
+ * loop takes (the last len mod 32 of each thread's range of the buffer, at the
+ * reference worker's 4 threads on an AVX-512 host), where the product is
+ * rounded to bf16 as well (c10::BFloat16 arithmetic). NaN payloads are not
+ * part of the contract.
+ *   d_param, d_grad  device buffers of n_elems elements of dtype
+ *   d_out            device buffer of n_elems. It may BE d_param or d_grad (in
+ *                    place); any other overlap is DLSIM_E_ARG
+ *   lr, weight_decay the Python floats; negative or NaN is DLSIM_E_ARG
+ *   dtype            DLSIM_F32, DLSIM_BF16 or DLSIM_F64. DLSIM_F16 is
+ *                    DLSIM_E_DTYPE: PyTorch's CPU result for fp16 depends on
+ *                    its thread count, so callers run torch's own ops for it
+ * n_elems == 0 is a no-op. Any alignment is accepted; 16-byte-aligned buffers
+ * take the vector path. Stream-ordered.
+ */
+int dlsim_sgd_step(const void* d_param, const void* d_grad, void* d_out, size_t n_elems, double lr,
+                   double weight_decay, int dtype, void* stream);
+
+/*
+ * dlsim_sgd_step_tensors: dlsim_sgd_step over t separate (parameter,
+ * gradient, output) tensors, the zip of model_trainer.py:140-141 over a
+ * model's parameters() and its gradient list, in one launch per 64 tensors.
+ * Bit-identical to t dlsim_sgd_step calls in order (each tensor is its own
+ * buffer for the bf16 rule above). Host arrays of t entries; numels[k] == 0
+ * skips tensor k. Per tensor the aliasing rule of dlsim_sgd_step; lists in
+ * which one tensor's output shares bytes with another tensor's buffers run as
+ * t launches in order.
+ */
+int dlsim_sgd_step_tensors(int t, const void* const* d_params, const void* const* d_grads, void* const* d_outs,
+                           const size_t* numels, double lr, double weight_decay, int dtype, void* stream);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
