@@ -227,6 +227,84 @@ int check_sgd_buffers(const void* p, const void* g, const void* out, size_t nele
   return DLSIM_OK;
 }
 
+// The momentum-SGD step's dispatch (inst_sgdm.hip): arguments already checked;
+// b == nullptr (an entry of b for the tensors form) is a first step.
+hipError_t sgdm_flat(const void* p, const void* g, const void* b, void* pout, void* bout, size_t nelem, double lr,
+                     double mom, double wd, int dtype, hipStream_t st);
+hipError_t sgdm_tensors(int t, const void* const* p, const void* const* g, const void* const* b, void* const* pout,
+                        void* const* bout, const size_t* nelem, double lr, double mom, double wd, int dtype,
+                        hipStream_t st);
+
+// dtype and hyper-parameters of dlsim_sgd_momentum_step / _tensors
+int check_sgdm_scalars(double lr, double mom, double wd, int dtype) {
+  const int rc = check_sgd_scalars(lr, wd, dtype);
+  if (rc != DLSIM_OK) return rc;
+  if (!(mom > 0.0))
+    return fail(DLSIM_E_ARG, "momentum must be > 0 (got %g); momentum == 0 is dlsim_sgd_step on every step", mom);
+  return DLSIM_OK;
+}
+
+// One (param, grad, buf, param_out, buf_out) tuple: param_out may BE param and
+// buf_out may BE buf (in place; a lane reads every term of an element before
+// it writes); any other overlap among the five is rejected. buf may be null.
+int check_sgdm_buffers(const void* p, const void* g, const void* b, const void* pout, const void* bout, size_t nelem,
+                       size_t esz) {
+  if (nelem == 0) return DLSIM_OK;
+  if (!p || !g || !pout || !bout) return fail(DLSIM_E_ARG, "null parameter, gradient or output pointer");
+  static const char* const kNames[5] = {"parameter", "gradient", "momentum buffer", "parameter output",
+                                        "buffer output"};
+  const size_t bytes = nelem * esz;
+  const uintptr_t at[5] = {reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(g),
+                           reinterpret_cast<uintptr_t>(b), reinterpret_cast<uintptr_t>(pout),
+                           reinterpret_cast<uintptr_t>(bout)};
+  for (int i = 0; i < 5; ++i)
+    for (int j = i + 1; j < 5; ++j) {
+      if (!at[i] || !at[j]) continue;  // no buffer yet
+      const bool in_place = (i == 0 && j == 3) || (i == 2 && j == 4);
+      if (in_place && at[i] == at[j]) continue;
+      if (at[i] < at[j] + bytes && at[j] < at[i] + bytes)
+        return fail(DLSIM_E_ARG, "the %s overlaps the %s", kNames[j], kNames[i]);
+    }
+  return DLSIM_OK;
+}
+
+// Whether buffers of two different tensors of a momentum-step list share
+// bytes (conservative: shared inputs count too). One sorted sweep.
+bool sgdm_cross_overlap(int t, const void* const* p, const void* const* g, const void* const* b,
+                        void* const* pout, void* const* bout, const size_t* numels, size_t esz) {
+  struct Iv {
+    uintptr_t lo, hi;
+    int task;
+  };
+  std::vector<Iv> iv;
+  iv.reserve(static_cast<size_t>(t) * 5);
+  for (int k = 0; k < t; ++k) {
+    if (numels[k] == 0) continue;
+    const size_t bytes = numels[k] * esz;
+    const void* const five[5] = {p[k], g[k], b[k], pout[k], bout[k]};
+    for (const void* q : five)
+      if (q) iv.push_back({reinterpret_cast<uintptr_t>(q), reinterpret_cast<uintptr_t>(q) + bytes, k});
+  }
+  std::sort(iv.begin(), iv.end(), [](const Iv& x, const Iv& y) { return x.lo < y.lo; });
+  // the furthest end so far, and the furthest among the other tasks
+  uintptr_t end1 = 0, end2 = 0;
+  int task1 = -1;
+  for (const Iv& x : iv) {
+    const uintptr_t other_end = task1 == x.task ? end2 : end1;
+    if (x.lo < other_end) return true;
+    if (x.task == task1) {
+      end1 = std::max(end1, x.hi);
+    } else if (x.hi > end1) {
+      end2 = end1;
+      end1 = x.hi;
+      task1 = x.task;
+    } else {
+      end2 = std::max(end2, x.hi);
+    }
+  }
+  return false;
+}
+
 }  // namespace dlsim_host
 
 // the per-policy entries live in the inst_*.hip units
@@ -971,6 +1049,51 @@ int dlsim_sgd_step_tensors(int t, const void* const* d_params, const void* const
     e = sgd_tensors(t, d_params, d_grads, d_outs, numels, lr, weight_decay, dtype, st);
   }
   return e == hipSuccess ? DLSIM_OK : hip_fail(e, "SGD step launch");
+}
+
+int dlsim_sgd_momentum_step(const void* d_param, const void* d_grad, const void* d_buf, void* d_param_out,
+                            void* d_buf_out, size_t n_elems, double lr, double momentum, double weight_decay,
+                            int dtype, void* stream) {
+  g_err.clear();
+  int rc = check_sgdm_scalars(lr, momentum, weight_decay, dtype);
+  if (rc == DLSIM_OK)
+    rc = check_sgdm_buffers(d_param, d_grad, d_buf, d_param_out, d_buf_out, n_elems, elem_bytes(dtype));
+  if (rc != DLSIM_OK || n_elems == 0) return rc;
+  const hipError_t e = sgdm_flat(d_param, d_grad, d_buf, d_param_out, d_buf_out, n_elems, lr, momentum, weight_decay,
+                                 dtype, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "momentum SGD step launch");
+}
+
+int dlsim_sgd_momentum_step_tensors(int t, const void* const* d_params, const void* const* d_grads,
+                                    const void* const* d_bufs, void* const* d_params_out, void* const* d_bufs_out,
+                                    const size_t* numels, double lr, double momentum, double weight_decay, int dtype,
+                                    void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_sgdm_scalars(lr, momentum, weight_decay, dtype);
+  if (rc != DLSIM_OK || t == 0) return rc;
+  if (!d_params || !d_grads || !d_bufs || !d_params_out || !d_bufs_out || !numels)
+    return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  for (int k = 0; k < t; ++k) {
+    rc = check_sgdm_buffers(d_params[k], d_grads[k], d_bufs[k], d_params_out[k], d_bufs_out[k], numels[k], esz);
+    if (rc != DLSIM_OK) return fail(rc, "tensor %d: %s", k, std::string(g_err).c_str());
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // One grid runs the tensors concurrently; t calls run them in order. They
+  // can differ only if two tensors' buffers share bytes: such lists go as t
+  // launches, in order.
+  hipError_t e = hipSuccess;
+  if (sgdm_cross_overlap(t, d_params, d_grads, d_bufs, d_params_out, d_bufs_out, numels, esz)) {
+    for (int k = 0; k < t && e == hipSuccess; ++k)
+      if (numels[k])
+        e = sgdm_flat(d_params[k], d_grads[k], d_bufs[k], d_params_out[k], d_bufs_out[k], numels[k], lr, momentum,
+                      weight_decay, dtype, st);
+  } else {
+    e = sgdm_tensors(t, d_params, d_grads, d_bufs, d_params_out, d_bufs_out, numels, lr, momentum, weight_decay,
+                     dtype, st);
+  }
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "momentum SGD step launch");
 }
 
 int dlsim_device_alloc(size_t nbytes, int flags, void** d_out, int* contiguous) {

@@ -16,16 +16,6 @@ struct SgdScalars {
   W nlr, wd;
 };
 
-inline float round_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return f;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  u &= 0xffff0000u;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 template <class Op>
 SgdScalars<dlsim::wt_t<Op>> sgd_scalars(double lr, double wd) {
   if constexpr (Op::kBytes == 8) {
@@ -33,7 +23,8 @@ SgdScalars<dlsim::wt_t<Op>> sgd_scalars(double lr, double wd) {
   } else if constexpr (Op::kBytes == 4) {
     return {static_cast<float>(-lr), static_cast<float>(wd)};
   } else {
-    return {round_bf16(static_cast<float>(-lr)), round_bf16(static_cast<float>(wd))};
+    return {dlsim::sgd_host_round_bf16(static_cast<float>(-lr)),
+            dlsim::sgd_host_round_bf16(static_cast<float>(wd))};
   }
 }
 

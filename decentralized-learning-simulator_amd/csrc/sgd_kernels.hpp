@@ -25,6 +25,8 @@
 // cases are separate instantiations (WD).
 #pragma once
 
+#include <cstring>
+
 #include "wreduce_kernels.hpp"
 
 namespace dlsim {
@@ -96,6 +98,18 @@ struct SgdBF16 {
   }
   __device__ static float finish(float a, float) { return a; }
 };
+
+// The same rounding on the host (nearest-even; NaN kept), for the scalars the
+// dispatch passes to the bf16 kernels.
+inline float sgd_host_round_bf16(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return f;
+  u += 0x7fffu + ((u >> 16) & 1u);
+  u &= 0xffff0000u;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
 
 // ---- which elements ATen's scalar loop takes ----------------------------------
 // TensorIterator runs a contiguous n-element op serially below 32768 elements

@@ -59,6 +59,8 @@ EXPORTS = (
     "dlsim_wreduce_mixed",
     "dlsim_sgd_step",
     "dlsim_sgd_step_tensors",
+    "dlsim_sgd_momentum_step",
+    "dlsim_sgd_momentum_step_tensors",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -183,6 +185,12 @@ def load() -> ctypes.CDLL:
         lib.dlsim_sgd_step_tensors.argtypes = [i, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                                ctypes.POINTER(sz), ctypes.c_double, ctypes.c_double, i, vp]
         lib.dlsim_sgd_step_tensors.restype = i
+        dbl = ctypes.c_double
+        lib.dlsim_sgd_momentum_step.argtypes = [vp, vp, vp, vp, vp, sz, dbl, dbl, dbl, i, vp]
+        lib.dlsim_sgd_momentum_step.restype = i
+        lib.dlsim_sgd_momentum_step_tensors.argtypes = [i] + [ctypes.POINTER(vp)] * 5 + [ctypes.POINTER(sz), dbl, dbl,
+                                                                                        dbl, i, vp]
+        lib.dlsim_sgd_momentum_step_tensors.restype = i
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -406,6 +414,44 @@ def sgd_step_tensors(params, grads, outs, lr: float, weight_decay: float, stream
                          [o.data_ptr() for o in outs], [o.numel() for o in outs], lr, weight_decay,
                          dtype_code(outs[0].dtype, single_task=True), _stream_handle(outs[0].device, stream))
     return outs
+
+
+def sgd_momentum_step(param, grad, buf, param_out, buf_out, lr: float, momentum: float, weight_decay: float,
+                      stream=None):
+    """dlsim_sgd_momentum_step: one step of torch.optim.SGD(lr, momentum > 0,
+    weight_decay) on flat device tensors. `buf` None: the first step
+    (buf_out = the gradient after weight decay). `param_out` may be `param`
+    and `buf_out` may be `buf`; `grad` is only read. Stream-ordered."""
+    for t in (param, grad, param_out, buf_out) + (() if buf is None else (buf,)):
+        if not t.is_cuda or t.device != param_out.device:
+            raise ValueError("the SGD step needs device tensors on one device (no CPU path)")
+        if t.dtype != param_out.dtype or t.numel() != param_out.numel() or not t.is_contiguous():
+            raise ValueError("parameter, gradient, buffer and outputs must be contiguous, same dtype and size")
+    _check("dlsim_sgd_momentum_step",
+           load().dlsim_sgd_momentum_step(param.data_ptr(), grad.data_ptr(), None if buf is None else buf.data_ptr(),
+                                          param_out.data_ptr(), buf_out.data_ptr(), param_out.numel(), float(lr),
+                                          float(momentum), float(weight_decay),
+                                          dtype_code(param_out.dtype, single_task=True),
+                                          _stream_handle(param_out.device, stream)))
+    return param_out, buf_out
+
+
+def sgd_momentum_step_tensors_raw(param_ptrs: Sequence[int], grad_ptrs: Sequence[int],
+                                  buf_ptrs: Sequence[Optional[int]], param_out_ptrs: Sequence[int],
+                                  buf_out_ptrs: Sequence[int], numels: Sequence[int], lr: float, momentum: float,
+                                  weight_decay: float, dtype: int, stream_handle) -> None:
+    """dlsim_sgd_momentum_step_tensors on raw device pointers (the caller
+    checked them); a None (or 0) in buf_ptrs is that tensor's first step."""
+    t = len(numels)
+    arr = ctypes.c_void_p * max(t, 1)
+    _check("dlsim_sgd_momentum_step_tensors",
+           load().dlsim_sgd_momentum_step_tensors(t, arr(*param_ptrs), arr(*grad_ptrs), arr(*buf_ptrs),
+                                                  arr(*param_out_ptrs), arr(*buf_out_ptrs),
+                                                  (ctypes.c_size_t * max(t, 1))(*numels), float(lr), float(momentum),
+                                                  float(weight_decay), dtype, stream_handle))
+
+
+SGD_MOMENTUM_TENSORS_PER_LAUNCH = 64  # csrc/sgdm_kernels.hpp kSgdmMaxTensors
 
 
 DLSIM_ALLOC_CONTIGUOUS = 1

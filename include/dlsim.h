@@ -555,6 +555,61 @@ int dlsim_sgd_step_tensors(int t, const void* const* d_params, const void* const
                            const size_t* numels, double lr, double weight_decay, int dtype, void* stream);
 
 /*
+ * dlsim_sgd_momentum_step: one step of the SGD the reference configures, with
+ * its momentum buffer carried from step to step, on one flat buffer:
+ *   dasklearn/optimizer/sgd.py             SGDOptimizer: torch.optim.SGD(lr,
+ *                                          momentum, weight_decay)
+ *   dasklearn/model_trainer.py:89-92,126   ModelTrainer.train: a new
+ *                                          SGDOptimizer, load_state_dict of the
+ *                                          previous round's, then
+ *                                          optimizer.optimizer.step() per
+ *                                          local step
+ * (dampening 0, no Nesterov, no maximize: all SGDOptimizer can set). Per
+ * element, as torch's CPU ops (torch.optim.sgd._single_tensor_sgd) round it:
+ *   g'        = grad + weight_decay * param   (skipped when weight_decay == 0)
+ *   d_buf_out = g'                            (d_buf == NULL: the first step)
+ *   d_buf_out = momentum * buf + g'           (every later step)
+ *   d_param_out = param - lr * d_buf_out
+ * The first and last lines are ONE fused multiply-add each, as in
+ * dlsim_sgd_step (fp32 and fp64 scalars, the bf16 two-rule layout, all as
+ * documented there). The buffer update is NOT fused: the product rounded, then
+ * a plain add; fp32: f32(f32(momentum) * buf) + g', fp64 the same in double;
+ * bf16: momentum stays fp32, the product is computed in fp32 and rounded to
+ * bf16, the sum is computed in fp32 and rounded to bf16, for every element.
+ *   d_param, d_grad  device buffers of n_elems elements of dtype; d_grad is
+ *                    never written
+ *   d_buf            the momentum buffer, or NULL on the first step
+ *   d_param_out      may BE d_param, and d_buf_out may BE d_buf (the normal
+ *   d_buf_out        in-place use); any other overlap among the five buffers
+ *                    is DLSIM_E_ARG
+ *   momentum         must be > 0 (zero, negative or NaN is DLSIM_E_ARG):
+ *                    momentum == 0 is dlsim_sgd_step on every step
+ *   lr, weight_decay, dtype   as dlsim_sgd_step (DLSIM_F16 is DLSIM_E_DTYPE)
+ * n_elems == 0 is a no-op. Any alignment is accepted; 16-byte-aligned buffers
+ * take the vector path. Argument errors are decided before any HIP call.
+ * Stream-ordered.
+ */
+int dlsim_sgd_momentum_step(const void* d_param, const void* d_grad, const void* d_buf, void* d_param_out,
+                            void* d_buf_out, size_t n_elems, double lr, double momentum, double weight_decay,
+                            int dtype, void* stream);
+
+/*
+ * dlsim_sgd_momentum_step_tensors: dlsim_sgd_momentum_step over t separate
+ * tensors (a model's parameters(), their .grad and their momentum buffers, the
+ * loop of torch's optimizer step behind model_trainer.py:126), in one launch
+ * per 64 tensors. d_bufs[k] == NULL is the first step of tensor k alone (a
+ * parameter that had no gradient so far). Bit-identical to t
+ * dlsim_sgd_momentum_step calls in order (each tensor is its own buffer for
+ * the bf16 rule). Host arrays of t entries; numels[k] == 0 skips tensor k.
+ * Per tensor the aliasing rule of dlsim_sgd_momentum_step; lists in which two
+ * tensors' buffers share bytes run as t launches in order.
+ */
+int dlsim_sgd_momentum_step_tensors(int t, const void* const* d_params, const void* const* d_grads,
+                                    const void* const* d_bufs, void* const* d_params_out, void* const* d_bufs_out,
+                                    const size_t* numels, double lr, double momentum, double weight_decay, int dtype,
+                                    void* stream);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for

@@ -32,6 +32,11 @@ shapes, dtypes, alignments, weights and special values, for a time budget.
               alignments, fp32 / bf16 / fp64, hyper-parameters, special values,
               sometimes in place) vs torch.optim.SGD on CPU tensors at the
               worker's 4 threads
+  sgdm        dlsim_sgd_momentum_step and dlsim_sgd_momentum_step_tensors: one
+              to three chained steps in place (random sizes, alignments, fp32 /
+              bf16 / fp64, lr, momentum, weight decay, special values, per-tensor
+              first flags) vs torch.optim.SGD(foreach=False) holding the same
+              buffers on the CPU at 4 threads: parameters and buffers
 
 Prints one JSON line with the case counts and the first failures (if any).
 
@@ -408,6 +413,55 @@ def sgd_case(rng, dtype):
     return ok, dict(kind="sgd", dtype=dtype, tensors=len(sizes), lr=lr, wd=wd, mode=mode)
 
 
+def sgdm_case(rng, dtype):
+    """The momentum-SGD step (both entries), parameters and momentum buffers,
+    against torch.optim.SGD(foreach=False) on the CPU at 4 threads, tensor by
+    tensor. Some tensors start with a buffer (a later step),
+    the others get theirs on the first step."""
+    sizes = [int(rng.choice([1, 2, 7, 8, 9, 31, 32, 33, 63, 1000, 4099, 32768, 32801, 65537, 300_001]))
+             for _ in range(int(rng.integers(1, 80)))]
+    if sum(sizes) > 2_000_000:
+        sizes = [min(s, 4099) for s in sizes]
+    lr = float(rng.choice([0.0, 1e-3, 0.05, 0.1, 1.0, float(np.exp(rng.uniform(-8, 1)))]))
+    wd = float(rng.choice([0.0, 0.0, 5e-4, 1e-2, float(np.exp(rng.uniform(-10, 0)))]))
+    mom = float(rng.choice([0.9, 0.9, 0.5, 0.99, float(rng.uniform(1e-3, 1.5))]))
+    steps = int(rng.integers(1, 4))
+    rows = [rand_values(rng, 2 + steps, s, dtype) for s in sizes]
+    ps = [to_dev([r[0]], dtype, int(rng.choice([0, 0, 1])))[0] for r in rows]
+    has = [bool(rng.random() < 0.5) for _ in sizes]
+    bs = [to_dev([r[1]], dtype, int(rng.choice([0, 0, 1])))[0] for r in rows]  # read only where has[k]
+    gs = [[to_dev([r[2 + s]], dtype, int(rng.choice([0, 0, 1])))[0] for r in rows] for s in range(steps)]
+    prev = torch.get_num_threads()
+    torch.set_num_threads(4)
+    try:
+        exps = []
+        for k in range(len(sizes)):
+            q = torch.nn.Parameter(ps[k].cpu())
+            opt = torch.optim.SGD([q], lr=lr, momentum=mom, weight_decay=wd, foreach=False)
+            if has[k]:
+                opt.state[q]["momentum_buffer"] = bs[k].cpu()
+            for s in range(steps):
+                q.grad = gs[s][k].cpu()
+                opt.step()
+            exps.append((bits(q.detach()).copy(), bits(opt.state[q]["momentum_buffer"]).copy()))
+    finally:
+        torch.set_num_threads(prev)
+    # single calls on copies, then the batch in place
+    sp, sb = [p.clone() for p in ps], [b.clone() for b in bs]
+    for s in range(steps):
+        for k in range(len(sizes)):
+            _native.sgd_momentum_step(sp[k], gs[s][k], sb[k] if has[k] or s else None, sp[k], sb[k], lr, mom, wd)
+    code = _native.dtype_code(DT[dtype], single_task=True)
+    for s in range(steps):
+        _native.sgd_momentum_step_tensors_raw(
+            [p.data_ptr() for p in ps], [g.data_ptr() for g in gs[s]],
+            [b.data_ptr() if has[k] or s else None for k, b in enumerate(bs)], [p.data_ptr() for p in ps],
+            [b.data_ptr() for b in bs], sizes, lr, mom, wd, code, torch.cuda.current_stream().cuda_stream)
+    ok = all(orc.same_bits(bits(p), e[0]) and orc.same_bits(bits(b), e[1]) and orc.same_bits(bits(p2), e[0])
+             and orc.same_bits(bits(b2), e[1]) for p, b, p2, b2, e in zip(ps, bs, sp, sb, exps))
+    return ok, dict(kind="sgdm", dtype=dtype, tensors=len(sizes), lr=lr, wd=wd, momentum=mom, steps=steps)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
@@ -417,7 +471,7 @@ def main():
     only = a.only.split(",") if a.only else None
     rng = np.random.default_rng(a.seed)
     counts = {"reduce": 0, "reduce_fast": 0, "tensors": 0, "batched": 0, "chunk_mean": 0, "modules": 0,
-              "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0}
+              "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0, "sgdm": 0}
     fails = []
     t_end = time.time() + a.seconds
     t_note = time.time() + 20
@@ -427,13 +481,13 @@ def main():
             t_note = time.time() + 20
         dtype = str(rng.choice(["f32", "bf16", "f16", "f64"]))
         which = rng.choice(["reduce", "tensors", "batched", "chunk_mean", "modules", "reconstruct",
-                            "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd"],
-                           p=[0.12, 0.1, 0.1, 0.13, 0.1, 0.1, 0.1, 0.05, 0.05, 0.04, 0.03, 0.08])
+                            "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd", "sgdm"],
+                           p=[0.1, 0.1, 0.1, 0.1, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.08, 0.08])
         if only:
             which = str(rng.choice(only))
-        if which == "sgd" and dtype == "f16":
+        if which in ("sgd", "sgdm") and dtype == "f16":
             dtype = "f32"  # fp16 has no SGD-step kernel (torch's CPU ops run it)
-        if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd"):
+        if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd", "sgdm"):
             dtype = "f32"  # fp64 reduces are the single-task entry (dlsim_wreduce_f64); chunk means take fp64
         try:
             if which == "reduce":
@@ -640,6 +694,9 @@ def main():
             elif which == "sgd":
                 ok, case = sgd_case(rng, dtype)
                 counts["sgd"] += 1
+            elif which == "sgdm":
+                ok, case = sgdm_case(rng, dtype)
+                counts["sgdm"] += 1
             elif which == "host_chunk":
                 from dasklearn_amd.arena import _side_streams
                 cpu_threads = int(rng.choice([1, 2, 4, 8, 16]))
