@@ -305,6 +305,36 @@ bool sgdm_cross_overlap(int t, const void* const* p, const void* const* g, const
   return false;
 }
 
+// The order-statistic reduce's dispatch (inst_robust.hip): arguments already checked.
+hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
+                       hipStream_t st);
+
+// dtype, fan-in and window of dlsim_robust_reduce / _tensors
+int check_robust_window(int n, int lo, int hi, int dtype) {
+  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  if (n < 1) return fail(DLSIM_E_ARG, "n must be >= 1 (got %d)", n);
+  if (n > DLSIM_MAX_ROBUST_INPUTS)
+    return fail(DLSIM_E_ARG, "n must be <= %d (got %d): the sorting network is held in registers",
+                DLSIM_MAX_ROBUST_INPUTS, n);
+  if (!(0 <= lo && lo < hi && hi <= n))
+    return fail(DLSIM_E_ARG, "the window must satisfy 0 <= lo < hi <= n (got lo %d, hi %d, n %d)", lo, hi, n);
+  return DLSIM_OK;
+}
+
+// One output range against its n inputs: any shared byte is rejected (exact
+// aliasing too: unlike the weighted reduce this is not declared in place).
+int check_robust_buffers(const void* const* in, size_t stride, int n, const void* out, size_t bytes) {
+  if (!out) return fail(DLSIM_E_ARG, "null output pointer");
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + bytes;
+  for (int i = 0; i < n; ++i) {
+    const void* p = in[static_cast<size_t>(i) * stride];
+    if (!p) return fail(DLSIM_E_ARG, "null input pointer at index %d", i);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
+    if (a0 < o1 && o0 < a0 + bytes) return fail(DLSIM_E_ARG, "output overlaps input %d", i);
+  }
+  return DLSIM_OK;
+}
+
 }  // namespace dlsim_host
 
 // the per-policy entries live in the inst_*.hip units
@@ -1094,6 +1124,62 @@ int dlsim_sgd_momentum_step_tensors(int t, const void* const* d_params, const vo
                      dtype, st);
   }
   return e == hipSuccess ? DLSIM_OK : hip_fail(e, "momentum SGD step launch");
+}
+
+int dlsim_robust_reduce(const void* const* d_inputs, int n, int lo, int hi, void* d_out, size_t n_elems, int dtype,
+                        void* stream) {
+  g_err.clear();
+  int rc = check_robust_window(n, lo, hi, dtype);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
+  if (n_elems == 0) return DLSIM_OK;
+  rc = check_robust_buffers(d_inputs, 1, n, d_out, n_elems * elem_bytes(dtype));
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = robust_flat(d_inputs, n, lo, hi, d_out, n_elems, dtype, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "robust reduce launch");
+}
+
+int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype, void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_robust_window(n, lo, hi, dtype);
+  if (rc != DLSIM_OK || t == 0) return rc;
+  if (!d_inputs || !n_elems || !out_off_bytes) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  const size_t ts = static_cast<size_t>(t);
+  // Every tensor's output range against every input of every tensor (the
+  // tensors run as launches in order on one stream) and against the other
+  // outputs; all before the first launch.
+  for (int k = 0; k < t; ++k) {
+    if (n_elems[k] == 0) continue;
+    if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out) + out_off_bytes[k], o1 = o0 + n_elems[k] * esz;
+    for (int j = 0; j < t; ++j) {
+      if (n_elems[j] == 0) continue;
+      const size_t bytes = n_elems[j] * esz;
+      for (int i = 0; i < n; ++i) {
+        const void* p = d_inputs[static_cast<size_t>(i) * ts + j];
+        if (!p) return fail(DLSIM_E_ARG, "null input pointer (model %d, tensor %d)", i, j);
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
+        if (a0 < o1 && o0 < a0 + bytes)
+          return fail(DLSIM_E_ARG, "output of tensor %d overlaps tensor %d of model %d", k, j, i);
+      }
+      const uintptr_t q0 = reinterpret_cast<uintptr_t>(d_out) + out_off_bytes[j];
+      if (j != k && q0 < o1 && o0 < q0 + bytes)
+        return fail(DLSIM_E_ARG, "outputs of tensors %d and %d overlap", k, j);
+    }
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const void* row[DLSIM_MAX_ROBUST_INPUTS];
+  for (int k = 0; k < t; ++k) {
+    if (n_elems[k] == 0) continue;
+    for (int i = 0; i < n; ++i) row[i] = d_inputs[static_cast<size_t>(i) * ts + k];
+    const hipError_t e =
+        robust_flat(row, n, lo, hi, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
+    if (e != hipSuccess) return hip_fail(e, "robust reduce launch");
+  }
+  return DLSIM_OK;
 }
 
 int dlsim_device_alloc(size_t nbytes, int flags, void** d_out, int* contiguous) {

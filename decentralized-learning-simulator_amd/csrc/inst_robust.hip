@@ -1,0 +1,83 @@
+// inst_robust.hip — instantiation unit: the order-statistic kernels
+// (robust_kernels.hpp) and their host dispatch, behind dlsim_robust_reduce and
+// dlsim_robust_reduce_tensors (dlsim_abi.hip checks the arguments).
+#include "robust_kernels.hpp"
+
+#include "dispatch.hpp"
+
+namespace dlsim_host __attribute__((visibility("hidden"))) {
+
+namespace {
+
+// Vectors per lane by capacity: one shape for every size. The rows' loads of
+// a tile are all in flight before the sort, CAP * VPT * 4 VGPRs of them, so
+// capacities up to 16 hold 16 vectors per lane (64 VGPRs, the tiled reduce's
+// VPT 4 at fan-in 4). Capacity 32 takes half a vector per lane
+// (k_robust_halves: 64 VGPRs of loads too), which keeps three or four waves
+// per SIMD where a whole vector left one or two (DESIGN.md §8j lists the
+// counts and the measurement).
+template <int CAP> constexpr int rob_vpt() { return CAP >= 16 ? 1 : 16 / CAP; }
+
+template <class Op, int CAP>
+hipError_t rob_launch_cap(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, hipStream_t st) {
+  constexpr int kVptCap = rob_vpt<CAP>();
+  constexpr int kStp = store_policy<Op>();
+  constexpr bool kHalves = CAP == 32;
+  bool aligned = aligned16(out);
+  for (int i = 0; i < n; ++i) aligned = aligned && aligned16(in[i]);
+  dlsim::RobSlots<CAP> s;
+  std::memset(&s, 0, sizeof(s));
+  if (!aligned) {
+    for (int i = 0; i < n; ++i) s.p[i] = in[i];
+    const size_t blocks = (nelem + dlsim::kBlock - 1) / dlsim::kBlock;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((dlsim::k_robust_scalar<Op, CAP>), dim3(static_cast<unsigned>(blocks)), dim3(dlsim::kBlock), 0,
+                       st, s, n, lo, hi, out, nelem);
+    return hipGetLastError();
+  }
+  // buffer stores take 32-bit byte offsets: longer outputs go as consecutive
+  // ranges (elements are independent; a multiple of every tile size)
+  const size_t range = kMaxLaunchOutBytes / Op::kBytes;
+  for (size_t o = 0; o < nelem; o += range) {
+    const size_t len = std::min(range, nelem - o);
+    for (int i = 0; i < n; ++i) s.p[i] = static_cast<const char*>(in[i]) + o * Op::kBytes;
+    void* const dst = static_cast<char*>(out) + o * Op::kBytes;
+    if constexpr (kHalves) {
+      const size_t nunit = len * Op::kBytes / 8;
+      const size_t blocks = nunit / dlsim::kBlock + 1;
+      if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((dlsim::k_robust_halves<Op, CAP>), dim3(static_cast<unsigned>(blocks)), dim3(dlsim::kBlock),
+                         0, st, s, n, lo, hi, dst, nunit, len);
+    } else {
+      const size_t nvec = len / Op::E;
+      const size_t blocks = nvec / (static_cast<size_t>(dlsim::kBlock) * kVptCap) + 1;
+      if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((dlsim::k_robust_tiles<Op, CAP, kVptCap, kStp>), dim3(static_cast<unsigned>(blocks)),
+                         dim3(dlsim::kBlock), 0, st, s, n, lo, hi, dst, nvec, len);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <class Op>
+hipError_t rob_launch(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, hipStream_t st) {
+  if (n <= 4) return rob_launch_cap<Op, 4>(in, n, lo, hi, out, nelem, st);
+  if (n <= 8) return rob_launch_cap<Op, 8>(in, n, lo, hi, out, nelem, st);
+  if (n <= 16) return rob_launch_cap<Op, 16>(in, n, lo, hi, out, nelem, st);
+  return rob_launch_cap<Op, 32>(in, n, lo, hi, out, nelem, st);
+}
+
+}  // namespace
+
+// 1 <= n <= 32, 0 <= lo < hi <= n, nelem > 0, dtype known, no overlap: checked by the caller
+hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
+                       hipStream_t st) {
+  if (dtype == DLSIM_F32) return rob_launch<dlsim::RobF32>(in, n, lo, hi, out, nelem, st);
+  if (dtype == DLSIM_BF16) return rob_launch<dlsim::RobBF16>(in, n, lo, hi, out, nelem, st);
+  if (dtype == DLSIM_F16) return rob_launch<dlsim::RobF16>(in, n, lo, hi, out, nelem, st);
+  return rob_launch<dlsim::RobF64>(in, n, lo, hi, out, nelem, st);
+}
+
+}  // namespace dlsim_host

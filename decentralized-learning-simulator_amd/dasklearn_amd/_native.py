@@ -61,6 +61,8 @@ EXPORTS = (
     "dlsim_sgd_step_tensors",
     "dlsim_sgd_momentum_step",
     "dlsim_sgd_momentum_step_tensors",
+    "dlsim_robust_reduce",
+    "dlsim_robust_reduce_tensors",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -191,6 +193,11 @@ def load() -> ctypes.CDLL:
         lib.dlsim_sgd_momentum_step_tensors.argtypes = [i] + [ctypes.POINTER(vp)] * 5 + [ctypes.POINTER(sz), dbl, dbl,
                                                                                         dbl, i, vp]
         lib.dlsim_sgd_momentum_step_tensors.restype = i
+        lib.dlsim_robust_reduce.argtypes = [ctypes.POINTER(vp), i, i, i, vp, sz, i, vp]
+        lib.dlsim_robust_reduce.restype = i
+        lib.dlsim_robust_reduce_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                                    i, i, vp, i, vp]
+        lib.dlsim_robust_reduce_tensors.restype = i
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -452,6 +459,53 @@ def sgd_momentum_step_tensors_raw(param_ptrs: Sequence[int], grad_ptrs: Sequence
 
 
 SGD_MOMENTUM_TENSORS_PER_LAUNCH = 64  # csrc/sgdm_kernels.hpp kSgdmMaxTensors
+
+
+MAX_ROBUST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_ROBUST_INPUTS
+
+
+def check_robust_fan_in(n: int) -> None:
+    """The order-statistic kernels sort their n inputs in registers."""
+    if n > MAX_ROBUST_INPUTS:
+        raise ValueError(f"the median and trimmed-mean kernels take at most {MAX_ROBUST_INPUTS} models "
+                         f"(got {n}): the sorting network is held in registers")
+
+
+def robust_reduce(inputs, lo: int, hi: int, out, stream=None):
+    """dlsim_robust_reduce: per element, the n inputs' values sorted ascending
+    (-0.0 < +0.0, NaN last), out = (s[lo] + ... + s[hi-1]) / (hi - lo). Flat
+    device tensors of one dtype (fp32, fp64, bf16, fp16) and size; `out` may
+    not share memory with an input. Stream-ordered."""
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_robust_fan_in(n)
+    numel = out.numel()
+    for t in list(inputs) + [out]:
+        if not t.is_cuda or t.device != out.device:
+            raise ValueError("the robust reduce needs device tensors on one device (no CPU path)")
+        if t.dtype != out.dtype or t.numel() != numel or not t.is_contiguous():
+            raise ValueError("inputs and output must be contiguous, same dtype and size")
+    _check("dlsim_robust_reduce",
+           load().dlsim_robust_reduce((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, int(lo), int(hi),
+                                      out.data_ptr(), numel, dtype_code(out.dtype, single_task=True),
+                                      _stream_handle(out.device, stream)))
+    return out
+
+
+def robust_reduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], out_offsets: Sequence[int],
+                              lo: int, hi: int, out_base: int, dtype: int, stream_handle) -> None:
+    """dlsim_robust_reduce_tensors on pointers the caller has already validated
+    (the arena path: every tensor checked against models[0]'s layout, on the
+    output's device, contiguous). in_ptrs model-major (tensor k of model i at
+    i * t + k); output tensor k at out_base + out_offsets[k] bytes."""
+    t = len(numels)
+    check_robust_fan_in(n)
+    _check("dlsim_robust_reduce_tensors",
+           load().dlsim_robust_reduce_tensors((ctypes.c_void_p * max(len(in_ptrs), 1))(*in_ptrs), n, t,
+                                              (ctypes.c_size_t * max(t, 1))(*numels),
+                                              (ctypes.c_size_t * max(t, 1))(*out_offsets), int(lo), int(hi),
+                                              out_base, dtype, stream_handle))
 
 
 DLSIM_ALLOC_CONTIGUOUS = 1

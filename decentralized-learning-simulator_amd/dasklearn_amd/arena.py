@@ -1432,6 +1432,88 @@ def _restride(out: nn.Module, layout: ParamLayout) -> nn.Module:
     return out
 
 
+def _robust_rows(all_params, idx, total: int, dt: torch.dtype, dev: torch.device):
+    """One device row per model holding its dtype group in layout order (host
+    models through one page-locked block and plain copies; models on another
+    device through .to). Returns (rows, page-locked block or None): the block
+    must outlive the copies queued on the current stream."""
+    n = len(all_params)
+    esz = _elem_size(dt)
+    stride = row_stride(total, esz)
+    flat = aligned_empty(n * stride, dt, dev, base_align(total * esz, esz))
+    rows = [flat[i * stride:i * stride + total] for i in range(n)]
+    pinned = None
+    for i, ps in enumerate(all_params):
+        parts = [ps[k].detach().reshape(-1) for k in idx]
+        if any(q.is_cuda for q in parts):
+            torch.cat([q.to(dev) for q in parts], out=rows[i])
+            continue
+        if pinned is None:
+            pinned = torch.empty(n * total, dtype=dt, pin_memory=True)
+        h = pinned[i * total:(i + 1) * total]
+        torch.cat(parts, out=h)
+        rows[i].copy_(h, non_blocking=True)
+    return rows, pinned
+
+
+def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Optional[bool] = None) -> nn.Module:
+    """The coordinate-wise order-statistic aggregate of `models` on the GPU
+    (dlsim_robust_reduce): per parameter element the n models' values are
+    sorted and the window [lo, hi) = lo_hi_fn(n) of them is averaged. As
+    aggregate_modules: a new module with copy.deepcopy(models[0]) semantics
+    (buffers and attributes are models[0]'s), the models only read, one launch
+    per dtype group, the result where models[0] lives unless to_host says
+    otherwise. A model whose parameter list differs from models[0]'s raises
+    ValueError (no zip semantics here); more than 32 models too.
+
+    Device-arena models are read in place, separate device tensors through
+    dlsim_robust_reduce_tensors, host models are copied into one device row
+    per model and dtype."""
+    model0 = models[0]  # IndexError for an empty list, as FedAvg
+    n = len(models)
+    _native.check_robust_fan_in(n)
+    lo, hi = lo_hi_fn(n)
+    layout, all_params, in_views = input_arenas(models)  # ZipMismatch is a ValueError
+    host_out = (not any(p.is_cuda for p in layout.params)) if to_host is None else to_host
+    dev = _target_device(all_params[0], device)
+    dix = dev.index
+    outs: Dict[torch.dtype, torch.Tensor] = {}
+    staged = False
+    keep = []  # page-locked blocks and contiguous copies the queued work reads
+    with torch.no_grad(), torch.cuda.device(dev):
+        raw_stream = torch._C._cuda_getCurrentRawStream(dix)
+        for dt, idx in layout.groups.items():
+            total = layout.totals[dt]
+            if total == 0:
+                outs[dt] = torch.empty(0, dtype=dt, device="cpu" if host_out else dev)
+                continue
+            out = outs[dt] = arena_empty(total, dt, dev)
+            views = in_views[dt]
+            if views is not None and all(v.get_device() == dix for v in views):
+                _native.robust_reduce(views, lo, hi, out)
+                continue
+            if all(ps[k].get_device() == dix for ps in all_params for k in idx):
+                copies, ptrs = _data_ptrs(all_params, idx)
+                keep.append(copies)
+                staged = staged or bool(copies)
+                _native.robust_reduce_tensors_raw(ptrs, n, layout.split_sizes[dt], layout.byte_offsets[dt], lo, hi,
+                                                  out.data_ptr(), _native.dtype_code(dt, single_task=True),
+                                                  raw_stream)
+                continue
+            rows, pinned = _robust_rows(all_params, idx, total, dt, dev)
+            keep.append(pinned)
+            staged = True
+            _native.robust_reduce(rows, lo, hi, out)
+        stream = torch.cuda.current_stream(dev)
+        if host_out:
+            left = {dt: a for dt, a in outs.items() if a.is_cuda}
+            outs.update(arenas_to_host(left, stream))  # waits for the stream
+        elif any(k is not None and len(k) for k in keep):
+            stream.synchronize()  # the staged copies' sources may go now
+    out = module_from_arenas(model0, layout, outs)
+    return _restride(out, layout) if staged else out
+
+
 def to_device_arena(model: nn.Module, device=None) -> nn.Module:
     """A copy of `model` (deepcopy semantics) whose parameters are views of one
     device arena per dtype — the form the aggregate reads in place. A plain

@@ -4,6 +4,8 @@
 selected through `SessionSettings.gradient_aggregation`,
 dasklearn/session_settings.py:40 and model_manager.py:37-39), so settings
 objects built for the reference select the HIP implementation unchanged.
+MEDIAN and TRIMMED_MEAN are new here (gradient_aggregation/robust.py): the
+reference has no such members.
 """
 from abc import abstractmethod
 from enum import IntEnum
@@ -14,6 +16,8 @@ from torch import nn
 
 class GradientAggregationMethod(IntEnum):
     FEDAVG = 1
+    MEDIAN = 2
+    TRIMMED_MEAN = 3
 
 
 class GradientAggregation:

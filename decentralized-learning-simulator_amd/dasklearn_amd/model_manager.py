@@ -2,7 +2,9 @@
 
 Collects incoming models keyed by peer id (first one wins, :27-32) and
 aggregates them with the method chosen by `settings.gradient_aggregation`
-(:37-43). The `dataset` argument is accepted and ignored, as the reference's
+(:37-43): FEDAVG = 1 as in the reference, and the two robust aggregators it
+does not have, MEDIAN = 2 and TRIMMED_MEAN = 3 (the latter trims
+`settings.aggregation_trim` values, default 1, at each end). The `dataset` argument is accepted and ignored, as the reference's
 aggregate task passes None (functions.py:99).
 """
 import logging
@@ -12,6 +14,7 @@ import torch.nn as nn
 
 from dasklearn_amd.gradient_aggregation import GradientAggregationMethod
 from dasklearn_amd.gradient_aggregation.fedavg import FedAvg
+from dasklearn_amd.gradient_aggregation.robust import CoordinateMedian, TrimmedMean
 
 
 class ModelManager:
@@ -34,6 +37,10 @@ class ModelManager:
         method = getattr(self.settings, "gradient_aggregation", GradientAggregationMethod.FEDAVG)
         if method == GradientAggregationMethod.FEDAVG:
             return FedAvg
+        if method == GradientAggregationMethod.MEDIAN:
+            return CoordinateMedian
+        if method == GradientAggregationMethod.TRIMMED_MEAN:
+            return TrimmedMean.with_trim(getattr(self.settings, "aggregation_trim", 1))
         return None  # the reference returns None for unknown methods too
 
     def aggregate_trained_models(self, weights: List[float] = None) -> Optional[nn.Module]:

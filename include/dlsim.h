@@ -610,6 +610,57 @@ int dlsim_sgd_momentum_step_tensors(int t, const void* const* d_params, const vo
                                     void* stream);
 
 /*
+ * dlsim_robust_reduce: coordinate-wise order-statistic reduce of n flat
+ * buffers, the arithmetic of the coordinate median and the trimmed mean.
+ *
+ * New: the reference has one aggregator, FedAvg
+ * (dasklearn/gradient_aggregation/fedavg.py:10-26), behind its plugin point
+ * (gradient_aggregation/__init__.py:8-17, model_manager.py:37-39). This entry
+ * implements what a second and third plugin there compute; it replaces no
+ * reference code. Per element j, over the n values d_inputs[i][j]:
+ *   s   = the values sorted ascending in the total order
+ *           -Inf < ... < -0.0 < +0.0 < ... < +Inf < NaN
+ *         (every NaN, whatever its sign or payload, is largest and equal to
+ *         every other NaN)
+ *   acc = s[lo];  for k = lo+1 .. hi-1: acc = acc + s[k]
+ *   d_out[j] = acc / (hi - lo)     (a NaN result: the dtype's canonical quiet NaN)
+ * fp32: fp32 adds and one IEEE fp32 division, nothing fused; fp64: the same in
+ * double; bf16 and fp16: the values widened to fp32 (exact), adds and division
+ * in fp32, ONE rounding to the dtype, nearest-even (not the per-step rounding
+ * of DLSIM_EXACT: there is no reference to match). lo = (n-1)/2, hi = lo+1 is
+ * the lower median, bit-identical to one of the inputs; lo = b, hi = n-b the
+ * mean trimmed by b values at each end.
+ *   d_inputs   host array of n device pointers (n_elems elements of dtype each)
+ *   n          1 <= n <= DLSIM_MAX_ROBUST_INPUTS (the sorting network lives in
+ *              registers); n == 1 copies, NaNs canonicalised
+ *   lo, hi     0 <= lo < hi <= n
+ *   d_out      device buffer of n_elems; it must share no byte with an input
+ *              (DLSIM_E_ARG; not even d_out == d_inputs[i])
+ *   dtype      all four of enum dlsim_dtype
+ * n_elems == 0 is a no-op. Any alignment is accepted; 16-byte-aligned buffers
+ * take the vector path. Argument errors are decided before any HIP call.
+ * Stream-ordered.
+ */
+#define DLSIM_MAX_ROBUST_INPUTS 32
+int dlsim_robust_reduce(const void* const* d_inputs, int n, int lo, int hi, void* d_out, size_t n_elems, int dtype,
+                        void* stream);
+
+/*
+ * dlsim_robust_reduce_tensors: dlsim_robust_reduce over t separate tensors per
+ * model (a device model whose parameters() are separate tensors), written into
+ * one output arena, in one call: one launch per non-empty tensor, in order.
+ *   d_inputs       host array of n*t device pointers, model-major:
+ *                  d_inputs[i*t + k] = tensor k of model i
+ *   n_elems        host array of t element counts (0 skips the tensor)
+ *   out_off_bytes  host array of t byte offsets into d_out
+ * Bit-identical to t dlsim_robust_reduce calls. No output range may share a
+ * byte with any input of any tensor, or with another output range
+ * (DLSIM_E_ARG, decided for the whole list before the first launch).
+ */
+int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype, void* stream);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for

@@ -37,6 +37,11 @@ shapes, dtypes, alignments, weights and special values, for a time budget.
               bf16 / fp64, lr, momentum, weight decay, special values, per-tensor
               first flags) vs torch.optim.SGD(foreach=False) holding the same
               buffers on the CPU at 4 threads: parameters and buffers
+  robust      dlsim_robust_reduce and dlsim_robust_reduce_tensors (the
+              coordinate median and trimmed mean): random fan-in 1..32, window,
+              dtype (all four), size, alignment of every input and of the
+              output, special values, vs tests/_robust_util.py's restatement of
+              the contract
 
 Prints one JSON line with the case counts and the first failures (if any).
 
@@ -52,7 +57,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "decentralized-learning-simulator_amd")):
+for p in (ROOT, os.path.join(ROOT, "decentralized-learning-simulator_amd"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -462,6 +467,54 @@ def sgdm_case(rng, dtype):
     return ok, dict(kind="sgdm", dtype=dtype, tensors=len(sizes), lr=lr, wd=wd, momentum=mom, steps=steps)
 
 
+def robust_case(rng, dtype):
+    """The order-statistic reduce (both entries) against the CPU restatement
+    of its contract, bit for bit."""
+    import _robust_util as ru
+    dt = DT[dtype]
+    n = int(rng.choice([1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, int(rng.integers(1, 33))]))
+    kind = str(rng.choice(["median", "trim", "any"]))
+    if kind == "median":
+        lo = (n - 1) // 2
+        hi = lo + 1
+    elif kind == "trim":
+        lo = int(rng.integers(0, (n - 1) // 2 + 1))
+        hi = n - lo
+    else:
+        lo = int(rng.integers(0, n))
+        hi = int(rng.integers(lo + 1, n + 1))
+    sizes = [int(rng.choice([1, 2, 3, 7, 8, 9, 63, 255, 1000, 1025, 4099, 65537, 300_001]))
+             for _ in range(int(rng.integers(1, 6)))]
+    if n * sum(sizes) > 3_000_000:
+        sizes = [min(s, 4099) for s in sizes]
+    total = sum(sizes)
+    xs = ru.random_rows(dt, n, total, int(rng.integers(0, 1 << 31)), special_frac=float(rng.choice([0.0, 0.02, 0.3])))
+    if rng.random() < 0.5:  # another magnitude (exact for finite values, away from overflow)
+        scale = float(2.0 ** int(rng.integers(-12, 8)))
+        xs = [x * scale for x in xs]
+    exp = ru.window_mean(xs, lo, hi)
+
+    def dev(x):
+        off = int(rng.choice([0, 0, 1, 3]))
+        buf = torch.empty(x.numel() + off, dtype=dt, device="cuda")
+        buf[off:].copy_(x)
+        return buf[off:]
+    flat = [dev(x) for x in xs]
+    out = dev(torch.zeros(total, dtype=dt))
+    _native.robust_reduce(flat, lo, hi, out)
+    ok = ru.same_bits(out.cpu(), exp)
+    # the same model as separate tensors, into one output arena
+    offs = [int(o) for o in np.concatenate([[0], np.cumsum(sizes)])[:-1]]
+    parts = [[dev(x[o:o + k]) for o, k in zip(offs, sizes)] for x in xs]
+    out2 = dev(torch.zeros(total, dtype=dt))
+    esz = out2.element_size()
+    _native.robust_reduce_tensors_raw([t.data_ptr() for row in parts for t in row], n, sizes, [o * esz for o in offs],
+                                      lo, hi, out2.data_ptr(), _native.dtype_code(dt, single_task=True),
+                                      torch.cuda.current_stream().cuda_stream)
+    ok = ok and ru.same_bits(out2.cpu(), exp)
+    return ok, dict(kind="robust", dtype=dtype, n=n, lo=lo, hi=hi, sizes=sizes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
@@ -471,7 +524,8 @@ def main():
     only = a.only.split(",") if a.only else None
     rng = np.random.default_rng(a.seed)
     counts = {"reduce": 0, "reduce_fast": 0, "tensors": 0, "batched": 0, "chunk_mean": 0, "modules": 0,
-              "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0, "sgdm": 0}
+              "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0, "sgdm": 0,
+              "robust": 0}
     fails = []
     t_end = time.time() + a.seconds
     t_note = time.time() + 20
@@ -481,13 +535,13 @@ def main():
             t_note = time.time() + 20
         dtype = str(rng.choice(["f32", "bf16", "f16", "f64"]))
         which = rng.choice(["reduce", "tensors", "batched", "chunk_mean", "modules", "reconstruct",
-                            "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd", "sgdm"],
-                           p=[0.1, 0.1, 0.1, 0.1, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.08, 0.08])
+                            "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd", "sgdm", "robust"],
+                           p=[0.085, 0.085, 0.085, 0.085, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.08, 0.08, 0.06])
         if only:
             which = str(rng.choice(only))
         if which in ("sgd", "sgdm") and dtype == "f16":
             dtype = "f32"  # fp16 has no SGD-step kernel (torch's CPU ops run it)
-        if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd", "sgdm"):
+        if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd", "sgdm", "robust"):
             dtype = "f32"  # fp64 reduces are the single-task entry (dlsim_wreduce_f64); chunk means take fp64
         try:
             if which == "reduce":
@@ -697,6 +751,9 @@ def main():
             elif which == "sgdm":
                 ok, case = sgdm_case(rng, dtype)
                 counts["sgdm"] += 1
+            elif which == "robust":
+                ok, case = robust_case(rng, dtype)
+                counts["robust"] += 1
             elif which == "host_chunk":
                 from dasklearn_amd.arena import _side_streams
                 cpu_threads = int(rng.choice([1, 2, 4, 8, 16]))
