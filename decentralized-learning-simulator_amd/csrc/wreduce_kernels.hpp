@@ -675,10 +675,11 @@ struct PreSlots {
 // profiles/r05s/ .. r05y/).
 //
 // R is a runtime argument (uniform, 1 <= R <= RMAX): the loads of U rows
-// issue back to back, then fold (a row past R re-reads row r0, which the
-// same wave's first load already brings in: no extra HBM traffic); the
-// compiler must not hoist later groups' loads above the fold (NF * RMAX live
-// vectors would spill), hence the barrier per group. Uniform `if`s instead
+// are written back to back, then the fold (where the compiler splits them,
+// and what the compiled-R form issues instead: defer_rows_c; a row past R
+// re-reads row r0, which the same wave's first load already brings in: no
+// extra HBM traffic); the compiler must not hoist later groups' loads above
+// the fold (NF * RMAX live vectors would spill), hence the barrier per group. Uniform `if`s instead
 // of `break`s keep the loops unrolled and res[] in VGPRs.
 constexpr int kDeferBlock = 512;
 // U rows' vectors of one group of inputs [i0, i0 + cnt) (cnt <= G; NF > 0: all
@@ -712,6 +713,22 @@ __device__ __forceinline__ void defer_fold_group(const S& s, int i0, int cnt, si
 }
 // Compile-time R (RC): every row group and store unguarded. NF == 0: the
 // grouped form (runtime fan-in in groups of G, input order).
+//
+// NF > 0, up to R = 24: a group's U rows are read in bursts of two inputs (4
+// loads, each stream's two rows adjacent), each burst folded before the next
+// issues. Less in flight per wave is faster here, not slower. Written as one
+// burst of NF * U loads, the compiler issues most groups as input 0's two
+// rows, a wait for the fold's x0 * 0 seed, then the other inputs; pinning the
+// NF * U loads together lost 0.45 us of the north star's 61.2, and keeping
+// two or three rows rolling lost 1.7-1.9, while bursts of two inputs gain
+// 1.0-1.2 us there and 2.5 % on its 2- and 4-rank slices (DESIGN.md §5e, §8;
+// profiles/r07_defer_bursts/). At R = 30 (8 x 44.7 M, several rounds of
+// blocks) they lose 0.7 %, and no pinned form beat the compiler's own split:
+// above R = 24 the group stays one burst, left to the scheduler. The
+// scheduling barriers keep a burst's loads together and its fold behind them;
+// the empty asm ties the fold to its place through the accumulators, never
+// through a loaded register, which would wait for it.
+template <int NF, int RC> constexpr int defer_burst() { return RC <= 24 ? 2 : NF; }
 template <class Op, class S, int NF, int G, int RC, int U, int STP>
 __device__ __forceinline__ void defer_rows_c(const S& s, int n, const OutRef& o, size_t base) {
   static_assert(RC % U == 0, "whole row groups");
@@ -725,27 +742,56 @@ __device__ __forceinline__ void defer_rows_c(const S& s, int n, const OutRef& o,
         defer_fold_group<Op, S, 0, G, U>(s, i0, (n - i0) < G ? (n - i0) : G, base, r0, RC, false, a);
 #pragma unroll
       for (int u = 0; u < U; ++u) res[r0 + u] = pack<Op>(a[u][0], s.divisor());
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      continue;
-    }
-    constexpr int K = NF > 0 ? NF : 1;
-    u32x4 x[K][U];
+    } else if constexpr (defer_burst<NF, RC>() < NF) {
+      constexpr int K = defer_burst<NF, RC>();
+      acc_t<Op> a[U][1][Op::E];
 #pragma unroll
-    for (int i = 0; i < K; ++i)
+      for (int i0 = 0; i0 < NF; i0 += K) {
+        u32x4 x[K][U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) x[i][u] = ld16<1>(s.ptr(i), base + static_cast<size_t>(r0 + u) * kDeferBlock);
+        for (int g = 0; g < K; ++g)
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      acc_t<Op> a[1][Op::E];
-      const u32x4 x0[1] = {x[0][u]};
-      init_tile<Op, 1>(a, x0, false);
+          for (int u = 0; u < U; ++u)
+            if (i0 + g < NF) x[g][u] = ld16<1>(s.ptr(i0 + g), base + static_cast<size_t>(r0 + u) * kDeferBlock);
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < K; ++i) {
-        const u32x4 xi[1] = {x[i][u]};
-        fold_tile<Op, 1>(a, s.wt(i), xi);
+        for (int u = 0; u < U; ++u) {
+          if (i0 == 0) {
+            const u32x4 x0[1] = {x[0][u]};
+            init_tile<Op, 1>(a[u], x0, false);
+          }
+#pragma unroll
+          for (int g = 0; g < K; ++g)
+            if (i0 + g < NF) {
+              const u32x4 xg[1] = {x[g][u]};
+              fold_tile<Op, 1>(a[u], s.wt(i0 + g), xg);
+            }
+#pragma unroll
+          for (int e = 0; e < Op::E; ++e) asm volatile("" : "+v"(a[u][0][e]) : : "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
-      res[r0 + u] = pack<Op>(a[0], s.divisor());
+#pragma unroll
+      for (int u = 0; u < U; ++u) res[r0 + u] = pack<Op>(a[u][0], s.divisor());
+    } else {
+      u32x4 x[NF][U];
+#pragma unroll
+      for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[i][u] = ld16<1>(s.ptr(i), base + static_cast<size_t>(r0 + u) * kDeferBlock);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        acc_t<Op> a[1][Op::E];
+        const u32x4 x0[1] = {x[0][u]};
+        init_tile<Op, 1>(a, x0, false);
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+          const u32x4 xi[1] = {x[i][u]};
+          fold_tile<Op, 1>(a, s.wt(i), xi);
+        }
+        res[r0 + u] = pack<Op>(a[0], s.divisor());
+      }
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
