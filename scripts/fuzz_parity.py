@@ -67,6 +67,8 @@ import torch  # noqa: E402
 from dasklearn_amd import _native  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
+import _edge_util as eu  # noqa: E402  (tests/: guard bands around the outputs)
+
 DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f64": torch.float64}
 
 
@@ -553,16 +555,21 @@ def main():
                 w = rand_weights(rng, n, dtype)
                 fast = rng.random() < 0.2  # one pass for every n: one final rounding
                 in_place = rng.random() < 0.15
+                guard = None
                 if in_place:
                     out = xs[int(rng.integers(0, n))]
                 else:
-                    zero = np.zeros(p, dtype={"f32": np.float32, "f64": np.float64}.get(dtype, np.uint16))
-                    out = to_dev([zero], dtype, int(rng.choice([0, 0, 1])))[0]
+                    esz = eu.ESIZE[dtype]  # a guarded output, one element off alignment at times
+                    guard = eu.guarded(p * esz, dtype, "cuda", offset=esz * int(rng.choice([0, 0, 1])))
+                    out = guard.view
                 _native.wreduce(xs, w, out, _native.DLSIM_FAST if fast else _native.DLSIM_EXACT)
                 exp = orc.wreduce(list(rows), w, dtype, "fast" if fast else "exact")
                 ok = orc.same_bits(bits(out), exp)
+                dirty = eu.check_guards(guard, limit=8) if guard is not None else []
                 counts["reduce_fast" if fast else "reduce"] += 1
                 case = dict(kind="reduce", dtype=dtype, n=n, p=p, off=off, fast=bool(fast), in_place=bool(in_place))
+                if dirty:
+                    ok, case["guard_bytes_written"] = False, dirty
                 if not ok:
                     case["diff"] = first_diff(bits(out), exp, rows, w)
             elif which == "tensors":
@@ -581,7 +588,7 @@ def main():
                 counts["tensors"] += 1
                 case = dict(kind="tensors", dtype=dtype, n=n, sizes=len(sizes))
             elif which == "batched":
-                tasks, exps = [], []
+                tasks, exps, guards = [], [], []
                 chain = rng.random() < 0.3
                 p_chain = int(rng.choice([1, 5, 100, 4097]))
                 for _ in range(int(rng.integers(1, 60))):
@@ -591,7 +598,8 @@ def main():
                     xs = to_dev(rows, dtype, int(rng.choice([0, 0, 0, 1])))
                     rows = list(rows)
                     w = rand_weights(rng, n)
-                    out = torch.empty(p, dtype=DT[dtype], device="cuda")
+                    guards.append(eu.guarded(p * eu.ESIZE[dtype], dtype, "cuda"))
+                    out = guards[-1].view
                     if chain and tasks and rng.random() < 0.5:
                         # read an earlier task's output (its result, in task order)
                         j = int(rng.integers(0, len(tasks)))
@@ -616,7 +624,10 @@ def main():
                 ok = all(oks)
                 counts["batched"] += 1
                 case = dict(kind="batched", dtype=dtype, tasks=len(tasks))
-                if not ok:
+                dirty = [(i, d) for i, g in enumerate(guards) for d in eu.check_guards(g, limit=4)]
+                if dirty:  # (a guarded output a later task replaced is never written: its guards stay clean)
+                    ok, case["guard_bytes_written"] = False, dirty[:8]
+                if False in oks:
                     i = oks.index(False)
                     e, rows, n, p = exps[i]
                     case.update(task=i, n=n, p=p, diff=first_diff(bits(tasks[i][2]), e, rows, tasks[i][1]))
@@ -784,7 +795,7 @@ def main():
                             cpu_threads=cpu_threads, side=side)
             else:
                 threads = int(rng.choice([1, 2, 4, 8, 16]))
-                tasks, exps = [], []
+                tasks, exps, guards = [], [], []
                 for _ in range(int(rng.integers(1, 24))):
                     m = int(rng.choice([1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 31, 33, 64, 100, 250]))
                     n = int(rng.choice([1, 2, 3, 4, 7, 8, 9, 31, 32, 33, 95, 1000, 8193, 100_003]))
@@ -792,13 +803,16 @@ def main():
                         n = int(rng.choice([1, 7, 33, 1000]))
                     rows = rand_values(rng, m, n, dtype)
                     xs = to_dev(rows, dtype, int(rng.choice([0, 0, 0, 1])))
-                    out = torch.empty(n, dtype=DT[dtype], device="cuda")
-                    tasks.append((xs, out))
+                    guards.append(eu.guarded(n * eu.ESIZE[dtype], dtype, "cuda"))
+                    tasks.append((xs, guards[-1].view))
                     exps.append(orc.chunk_mean(list(rows), dtype, threads))
                 _native.chunk_mean_batched(tasks, threads=threads)
                 ok = all(orc.same_bits(bits(t[1]), e) for t, e in zip(tasks, exps))
                 counts["chunk_mean"] += 1
                 case = dict(kind="chunk_mean", dtype=dtype, tasks=len(tasks), threads=threads)
+                dirty = [(i, d) for i, g in enumerate(guards) for d in eu.check_guards(g, limit=4)]
+                if dirty:
+                    ok, case["guard_bytes_written"] = False, dirty[:8]
         except Exception as e:  # an unexpected exception is a failure too
             ok, case = False, dict(kind=str(which), dtype=str(dtype), error=f"{type(e).__name__}: {e}"[:300])
         if not ok:
