@@ -335,6 +335,37 @@ int check_robust_buffers(const void* const* in, size_t stride, int n, const void
   return DLSIM_OK;
 }
 
+// The pairwise squared-distance dispatch (inst_pairdist.hip): arguments already checked.
+hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
+                         hipStream_t st);
+void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
+
+// dtype, fan-in and flag of dlsim_pairwise_sqdist / _tensors
+int check_pairdist_scalars(int n, int dtype, int accumulate) {
+  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  if (n < 1) return fail(DLSIM_E_ARG, "n must be >= 1 (got %d)", n);
+  if (n > DLSIM_MAX_PAIRDIST_INPUTS)
+    return fail(DLSIM_E_ARG, "n must be <= %d (got %d): the pairs' accumulators are held in registers",
+                DLSIM_MAX_PAIRDIST_INPUTS, n);
+  if (accumulate != 0 && accumulate != 1) return fail(DLSIM_E_ARG, "accumulate must be 0 or 1 (got %d)", accumulate);
+  return DLSIM_OK;
+}
+
+// The n inputs of one tensor (stride apart in `in`) against the matrix: no
+// null pointer, no byte shared with d2. The inputs may alias each other.
+// Zero-byte inputs are never read: any pointer will do (torch gives null).
+int check_pairdist_buffers(const void* const* in, size_t stride, int n, size_t bytes, const double* d2) {
+  if (bytes == 0) return DLSIM_OK;
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(d2), o1 = o0 + sizeof(double) * static_cast<size_t>(n) * n;
+  for (int i = 0; i < n; ++i) {
+    const void* p = in[static_cast<size_t>(i) * stride];
+    if (!p) return fail(DLSIM_E_ARG, "null input pointer at index %d", i);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
+    if (a0 < o1 && o0 < a0 + bytes) return fail(DLSIM_E_ARG, "the distance matrix overlaps input %d", i);
+  }
+  return DLSIM_OK;
+}
+
 }  // namespace dlsim_host
 
 // the per-policy entries live in the inst_*.hip units
@@ -1179,6 +1210,55 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
         robust_flat(row, n, lo, hi, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
     if (e != hipSuccess) return hip_fail(e, "robust reduce launch");
   }
+  return DLSIM_OK;
+}
+
+int dlsim_pairwise_sqdist(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,
+                          void* stream) {
+  g_err.clear();
+  int rc = check_pairdist_scalars(n, dtype, accumulate);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
+  if (!d_d2) return fail(DLSIM_E_ARG, "null distance matrix pointer");
+  rc = check_pairdist_buffers(d_inputs, 1, n, n_elems * elem_bytes(dtype), d_d2);
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = pairdist_flat(d_inputs, n, n_elems, dtype, d_d2, accumulate, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "pairwise distance launch");
+}
+
+int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems, int dtype,
+                                  double* d_d2, int accumulate, void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_pairdist_scalars(n, dtype, accumulate);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_d2) return fail(DLSIM_E_ARG, "null distance matrix pointer");
+  if (t > 0 && (!d_inputs || !n_elems)) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t ts = static_cast<size_t>(t);
+  for (int k = 0; k < t; ++k) {
+    rc = check_pairdist_buffers(d_inputs + k, ts, n, n_elems[k] * elem_bytes(dtype), d_d2);
+    if (rc != DLSIM_OK) return fail(rc, "tensor %d: %s", k, std::string(g_err).c_str());
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (t == 0) {
+    const hipError_t e = pairdist_flat(nullptr, n, 0, dtype, d_d2, accumulate, st);
+    return e == hipSuccess ? DLSIM_OK : hip_fail(e, "pairwise distance launch");
+  }
+  const void* row[DLSIM_MAX_PAIRDIST_INPUTS];
+  for (int k = 0; k < t; ++k) {
+    for (int i = 0; i < n; ++i) row[i] = d_inputs[static_cast<size_t>(i) * ts + k];
+    const hipError_t e = pairdist_flat(row, n, n_elems[k], dtype, d_d2, k == 0 ? accumulate : 1, st);
+    if (e != hipSuccess) return hip_fail(e, "pairwise distance launch");
+  }
+  return DLSIM_OK;
+}
+
+int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks) {
+  g_err.clear();
+  const int rc = check_pairdist_scalars(n, dtype, 0);
+  if (rc != DLSIM_OK) return rc;
+  if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
+  pairdist_geometry(n, dtype, n_elems, tile_elems, blocks);
   return DLSIM_OK;
 }
 

@@ -1,0 +1,119 @@
+// inst_pairdist.hip — instantiation unit: the pairwise squared-distance
+// kernels (pairdist_kernels.hpp) and their host dispatch, behind
+// dlsim_pairwise_sqdist, dlsim_pairwise_sqdist_tensors and
+// dlsim_pairdist_geometry (dlsim_abi.hip checks the arguments).
+#include "pairdist_kernels.hpp"
+
+#include "dispatch.hpp"
+
+namespace dlsim_host __attribute__((visibility("hidden"))) {
+
+namespace {
+
+// Blocks of one launch, over all its units: four resident blocks (one wave
+// per SIMD each) on each of the 256 CUs of an MI355X. A constant, so that the
+// summation order is the same on every device.
+constexpr unsigned kPdGridBlocks = 1024;
+
+struct PdGeom {
+  int cap;          // rows of a diagonal unit: 4 or 8
+  bool cross;       // n > 8: diagonal and cross units in one launch
+  unsigned units;   // second grid dimension
+  unsigned active;  // units that hold at least one pair
+  size_t tile;      // elements a block takes per step
+  unsigned blocks;  // first grid dimension
+};
+
+// elems16: elements of a 16-byte vector; vec: every base is 16-byte aligned
+PdGeom pd_geometry(int n, int elems16, size_t nelem, bool vec) {
+  PdGeom g;
+  g.cap = n <= 4 ? 4 : dlsim::kPdGroup;
+  g.cross = n > dlsim::kPdGroup;
+  const unsigned groups = static_cast<unsigned>((n + dlsim::kPdGroup - 1) / dlsim::kPdGroup);
+  g.units = g.cross ? groups * groups : 1;  // G diagonal + 2 * G (G - 1) / 2 cross
+  g.active = 1;
+  if (g.cross) {
+    g.active = 0;
+    for (unsigned a = 0; a < groups; ++a) {
+      if (n - static_cast<int>(a) * dlsim::kPdGroup >= 2) ++g.active;
+      for (unsigned b = a + 1; b < groups; ++b)
+        for (int half = 0; half < 2; ++half)
+          if (n - static_cast<int>(b) * dlsim::kPdGroup - half * dlsim::kPdCross >= 1) ++g.active;
+    }
+  }
+  g.tile = static_cast<size_t>(dlsim::kBlock) * (vec ? elems16 : 1);
+  const size_t tiles = (nelem + g.tile - 1) / g.tile;
+  const size_t cap = kPdGridBlocks / g.active;
+  g.blocks = static_cast<unsigned>(std::min(cap, std::max<size_t>(tiles, 1)));
+  return g;
+}
+
+template <class Op, bool VEC>
+void pd_launch_main(const PdGeom& g, const dlsim::PdSlots& s, int n, size_t nelem, double* ws, hipStream_t st) {
+  const dim3 grid(g.blocks, g.units), block(dlsim::kBlock);
+  if (g.cross) hipLaunchKernelGGL((dlsim::k_pairdist<Op, 8, true, VEC>), grid, block, 0, st, s, n, nelem, ws);
+  else if (g.cap == 4) hipLaunchKernelGGL((dlsim::k_pairdist<Op, 4, false, VEC>), grid, block, 0, st, s, n, nelem, ws);
+  else hipLaunchKernelGGL((dlsim::k_pairdist<Op, 8, false, VEC>), grid, block, 0, st, s, n, nelem, ws);
+}
+
+// 2 <= n <= 32, nelem > 0
+template <class Op>
+hipError_t pd_run(const void* const* in, int n, size_t nelem, double* d2, int accumulate, hipStream_t st) {
+  bool vec = true;
+  for (int i = 0; i < n; ++i) vec = vec && aligned16(in[i]);
+  dlsim::PdSlots s;
+  std::memset(&s, 0, sizeof(s));
+  const int pairs = n * (n - 1) / 2;
+  const unsigned fin_blocks = static_cast<unsigned>((pairs + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
+  // Inputs too long for 32-bit byte offsets go as consecutive ranges (the
+  // launch limit of the library's other load paths); every range after the
+  // first accumulates.
+  const size_t range = kMaxLaunchOutBytes / Op::kBytes;
+  for (size_t o = 0; o < nelem; o += range) {
+    const size_t len = std::min(range, nelem - o);
+    for (int i = 0; i < n; ++i) s.p[i] = static_cast<const char*>(in[i]) + o * Op::kBytes;
+    const PdGeom g = pd_geometry(n, Op::E, len, vec);
+    // the blocks' partials: stream-ordered, as the fan-in table of the reduce
+    void* ws = nullptr;
+    hipError_t e = hipMallocAsync(&ws, sizeof(double) * dlsim::kPdSlots * g.units * g.blocks, st);
+    if (e != hipSuccess) return e;
+    if (vec) pd_launch_main<Op, true>(g, s, n, len, static_cast<double*>(ws), st);
+    else pd_launch_main<Op, false>(g, s, n, len, static_cast<double*>(ws), st);
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(dlsim::k_pairdist_finish, dim3(fin_blocks), dim3(dlsim::kBlock), 0, st,
+                         static_cast<const double*>(ws), g.blocks, n, g.cap, d2, (accumulate || o > 0) ? 1 : 0);
+      e = hipGetLastError();
+    }
+    const hipError_t e2 = hipFreeAsync(ws, st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+int pd_elems16(int dtype) { return dtype == DLSIM_F64 ? 2 : dtype == DLSIM_F32 ? 4 : 8; }
+
+}  // namespace
+
+// 1 <= n <= 32, dtype known, d2 apart from the inputs: checked by the caller
+hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
+                         hipStream_t st) {
+  if (n == 1 || nelem == 0) {  // no term: zeros, or nothing to add
+    if (accumulate) return hipSuccess;
+    return hipMemsetAsync(d2, 0, sizeof(double) * static_cast<size_t>(n) * n, st);
+  }
+  if (dtype == DLSIM_F32) return pd_run<dlsim::PdF32>(in, n, nelem, d2, accumulate, st);
+  if (dtype == DLSIM_BF16) return pd_run<dlsim::PdBF16>(in, n, nelem, d2, accumulate, st);
+  if (dtype == DLSIM_F16) return pd_run<dlsim::PdF16>(in, n, nelem, d2, accumulate, st);
+  return pd_run<dlsim::PdF64>(in, n, nelem, d2, accumulate, st);
+}
+
+// The 16-byte aligned path's tile and grid (no HIP call).
+void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks) {
+  const PdGeom g = pd_geometry(n, pd_elems16(dtype), nelem, true);
+  *tile_elems = g.tile;
+  *blocks = g.blocks;
+}
+
+}  // namespace dlsim_host

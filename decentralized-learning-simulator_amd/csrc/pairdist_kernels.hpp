@@ -1,0 +1,303 @@
+// pairdist_kernels.hpp — gfx950 kernels for the matrix of squared L2 distances
+// between n flat buffers: the primitive under Krum and
+// Multi-Krum (gradient_aggregation/krum.py) and the consensus distance of the
+// gossip literature. The reference has no such code: its one aggregator is
+// FedAvg (dasklearn/gradient_aggregation/fedavg.py).
+//
+// Contract, for i != j:  d2[i][j] = sum_e (double(x_i[e]) - double(x_j[e]))^2.
+// Every value is widened to double (exact for fp32, fp64, bf16, fp16), the
+// subtraction is a double subtraction and each term enters its accumulator
+// with one fma(d, d, acc), written out because the library is built with
+// -ffp-contract=off (hence policy names outside scripts/audit_isa.py's
+// POLICIES). The summation order is this file's: per lane over the tiles its
+// block strides over, then the 64 lanes of a wave (xor butterfly), the four
+// waves of a block in wave order, and in k_pairdist_finish the blocks (lane l
+// of a wave adds blocks l, l + 64, ... in order, then the same butterfly).
+// There is no float atomic: the order is a function of the grid alone, and
+// the grid is a function of (n, dtype, n_elems, alignment class) alone.
+//
+// Unlike every other kernel of the library this one reduces along the
+// parameter axis. Its input side is the tiled reduce's (wreduce_kernels.hpp):
+// 256-lane blocks, one 16-byte load per lane and row, every row's load of a
+// tile issued before the first use. Rows go in groups of 8 (kPdGroup):
+//   * a diagonal unit holds the pairs inside one group: 28 double accumulators
+//     per lane beside 8 loaded vectors;
+//   * a cross unit holds 8 rows of one group against 4 rows (kPdCross) of a
+//     later group: 32 accumulators beside 12 loaded vectors. (8 x 8 would be
+//     128 VGPRs of accumulators.)
+// n <= 8 is one diagonal unit and reads every row once (n <= 4: a 4-row unit
+// of 6 accumulators). Larger n is one launch whose second grid dimension is
+// the unit: G = ceil(n / 8) diagonal units, then two cross units per group
+// pair; a row is read once per unit it belongs to (about 2x at n = 16, 4x at
+// n = 32). Absent rows of a unit (n no multiple of the group) load nothing
+// and count as zeros; their slots are never read.
+//
+// A block strides over full tiles without bounds checks and keeps its
+// accumulators in registers until its end: per accumulator a 64-lane shuffle
+// reduce, the waves' sums through LDS, one store of the block's partials to
+// ws[(unit * kPdSlots + slot) * blocks + block]. k_pairdist_finish then takes
+// one wave per pair (i < j), adds the blocks' partials and stores the result
+// to d2[i][j] and d2[j][i] (or adds it to d2[i][j] and stores that to both).
+// The scalar form (VEC = false: one element per lane and row, any alignment)
+// shares all of this.
+#pragma once
+
+#include "wreduce_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace dlsim {
+
+constexpr int kPdMaxInputs = 32;
+constexpr int kPdGroup = 8;   // rows of a group (and of a diagonal unit)
+constexpr int kPdCross = 4;   // rows on the short side of a cross unit
+constexpr int kPdSlots = 32;  // partial sums a unit owns per block (28 or 6 used by a diagonal unit)
+
+// ---- element policies ---------------------------------------------------------
+// What unpack-style code needs to know of an element; the arithmetic is in
+// double for all of them.
+struct PdF32 {
+  static constexpr int E = 4;
+  static constexpr int kBytes = 4;
+  static constexpr int kFmt = kFmtF32;
+};
+struct PdF64 {
+  using T = double;
+  using W = double;
+  static constexpr int E = 2;
+  static constexpr int kBytes = 8;
+  static constexpr int kFmt = kFmtF32;
+};
+struct PdBF16 {
+  static constexpr int E = 8;
+  static constexpr int kBytes = 2;
+  static constexpr int kFmt = kFmtBF16;
+};
+struct PdF16 {
+  static constexpr int E = 8;
+  static constexpr int kBytes = 2;
+  static constexpr int kFmt = kFmtF16;
+};
+
+// The n <= 32 input pointers travel in the kernarg segment (scalar loads; a
+// unit indexes them with its wave-uniform first row).
+struct PdSlots {
+  const void* p[kPdMaxInputs];
+};
+
+// What a lane holds of one row between the load and the arithmetic: a 16-byte
+// vector (VEC) or one element in its accumulator type.
+template <class Op, bool VEC>
+struct PdRaw {
+  using type = u32x4;
+  static constexpr int EV = Op::E;
+  __device__ static type zero() { return u32x4{0u, 0u, 0u, 0u}; }
+};
+template <class Op>
+struct PdRaw<Op, false> {
+  using type = acc_t<Op>;
+  static constexpr int EV = 1;
+  __device__ static type zero() { return 0; }
+};
+
+// Item idx of a row (vector or element); zeros past `count` when CHECK.
+template <class Op, bool VEC, bool CHECK, int LDP>
+__device__ __forceinline__ typename PdRaw<Op, VEC>::type pd_load(const void* p, size_t idx, size_t count) {
+  typename PdRaw<Op, VEC>::type r = PdRaw<Op, VEC>::zero();
+  if (!CHECK || idx < count) {
+    if constexpr (VEC) r = ld16<LDP>(p, idx);
+    else r = load_elem<Op>(p, idx);
+  }
+  return r;
+}
+
+// Element e of a loaded item, widened to double (exact).
+template <class Op, bool VEC>
+__device__ __forceinline__ double pd_elem(const typename PdRaw<Op, VEC>::type& r, int e) {
+  if constexpr (!VEC) {
+    return static_cast<double>(r);
+  } else if constexpr (Op::kBytes == 8) {
+    return __builtin_bit_cast(double, static_cast<uint64_t>(r[2 * e]) | (static_cast<uint64_t>(r[2 * e + 1]) << 32));
+  } else if constexpr (Op::kBytes == 4) {
+    return static_cast<double>(__uint_as_float(r[e]));
+  } else if constexpr (Op::kFmt == kFmtF16) {
+    const uint32_t u = r[e / 2];
+    const uint16_t h = static_cast<uint16_t>((e & 1) ? (u >> 16) : (u & 0xffffu));
+    return static_cast<double>(__builtin_bit_cast(_Float16, h));
+  } else {
+    const uint32_t u = r[e / 2];
+    return static_cast<double>(__uint_as_float((e & 1) ? (u & 0xffff0000u) : (u << 16)));
+  }
+}
+
+// accumulators of a unit: RB == 0 is a diagonal unit over RA rows
+template <int RA, int RB> constexpr int pd_pairs() { return RB ? RA * RB : RA * (RA - 1) / 2; }
+// slot of the pair (i < j) inside a diagonal unit of RA rows (the finish kernel restates it)
+constexpr int pd_diag_slot(int ra, int i, int j) { return i * ra - i * (i + 1) / 2 + (j - i - 1); }
+
+// One item per lane and row: all loads first, then element by element the
+// rows' values widened and one subtraction and one fma per pair.
+template <class Op, int RA, int RB, bool VEC, bool CHECK, int LDP>
+__device__ __forceinline__ void pd_tile(const PdSlots& s, int a0, int na, int b0, int nb, size_t idx, size_t count,
+                                        double (&acc)[pd_pairs<RA, RB>()]) {
+  using Raw = PdRaw<Op, VEC>;
+  constexpr int kRB = RB ? RB : 1;
+  typename Raw::type ra[RA], rb[kRB];
+#pragma unroll
+  for (int i = 0; i < RA; ++i) {
+    ra[i] = Raw::zero();
+    if (i < na) ra[i] = pd_load<Op, VEC, CHECK, LDP>(s.p[a0 + i], idx, count);
+  }
+#pragma unroll
+  for (int j = 0; j < RB; ++j) {
+    rb[j] = Raw::zero();
+    if (j < nb) rb[j] = pd_load<Op, VEC, CHECK, LDP>(s.p[b0 + j], idx, count);
+  }
+#pragma unroll
+  for (int e = 0; e < Raw::EV; ++e) {
+    double xa[RA], xb[kRB];
+#pragma unroll
+    for (int i = 0; i < RA; ++i) xa[i] = pd_elem<Op, VEC>(ra[i], e);
+    if constexpr (RB == 0) {
+#pragma unroll
+      for (int i = 0; i < RA; ++i)
+#pragma unroll
+        for (int j = i + 1; j < RA; ++j) {
+          const double d = xa[i] - xa[j];
+          acc[pd_diag_slot(RA, i, j)] = __builtin_fma(d, d, acc[pd_diag_slot(RA, i, j)]);
+        }
+    } else {
+#pragma unroll
+      for (int j = 0; j < RB; ++j) xb[j] = pd_elem<Op, VEC>(rb[j], e);
+#pragma unroll
+      for (int i = 0; i < RA; ++i)
+#pragma unroll
+        for (int j = 0; j < RB; ++j) {
+          const double d = xa[i] - xb[j];
+          acc[i * RB + j] = __builtin_fma(d, d, acc[i * RB + j]);
+        }
+    }
+  }
+}
+
+// One unit of one block: rows a0 .. a0 + na (and b0 .. b0 + nb of a cross
+// unit) over this block's share of the items, then the block's partial sums
+// to ws[slot * gridDim.x + blockIdx.x]. Every block of a unit stores all its
+// slots, zeros where it had no tile. red: kBlock / 64 rows of kPdSlots.
+template <class Op, int RA, int RB, bool VEC, int LDP>
+__device__ __forceinline__ void pd_unit(const PdSlots& s, int a0, int na, int b0, int nb, size_t nelem,
+                                        double* __restrict__ ws, double (*red)[kPdSlots]) {
+  constexpr int NP = pd_pairs<RA, RB>();
+  constexpr int EV = PdRaw<Op, VEC>::EV;
+  static_assert(NP <= kPdSlots, "a unit's partials fit its slots");
+  double acc[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) acc[k] = 0.0;
+  const size_t items = nelem / EV;  // whole vectors, or elements
+  const size_t full = items / kBlock;
+  const size_t nblk = gridDim.x, b = blockIdx.x;
+  for (size_t t = b; t < full; t += nblk)
+    pd_tile<Op, RA, RB, VEC, false, LDP>(s, a0, na, b0, nb, t * kBlock + threadIdx.x, items, acc);
+  // the partial tile goes to the block next in the deal, the < E elements
+  // past the last whole vector to the last block (the one with the fewest tiles)
+  if (full * kBlock < items && full % nblk == b)
+    pd_tile<Op, RA, RB, VEC, true, LDP>(s, a0, na, b0, nb, full * kBlock + threadIdx.x, items, acc);
+  if constexpr (VEC) {
+    if (items * EV < nelem && b == nblk - 1)
+      pd_tile<Op, RA, RB, false, true, 0>(s, a0, na, b0, nb, items * EV + threadIdx.x, nelem, acc);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    const int k = threadIdx.x;
+    ws[static_cast<size_t>(k) * nblk + b] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// grid (blocks, units). CROSS = false: the one diagonal unit of n <= CAP rows
+// (CAP 4 or 8). CROSS = true (CAP 8, n > 8): units 0 .. G-1 are the groups'
+// diagonal units, unit G + 2 * pair + half the 8 rows of group ga against
+// rows 8 gb + 4 half .. + 4 of group gb, the pairs ga < gb numbered row by
+// row. Units without a pair of rows return at once.
+template <class Op, int CAP, bool CROSS, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_pairdist(const PdSlots s, int n, size_t nelem, double* __restrict__ ws) {
+  static_assert(kBlock == 256, "four waves: the block-end sum names them");
+  __shared__ double red[kBlock / 64][kPdSlots];
+  // rows read by several units stay cacheable; a single unit streams
+  constexpr int LDP = CROSS ? 0 : 1;
+  const int u = blockIdx.y;
+  double* const wsu = ws + static_cast<size_t>(u) * kPdSlots * gridDim.x;
+  if constexpr (!CROSS) {
+    pd_unit<Op, CAP, 0, VEC, LDP>(s, 0, n, 0, 0, nelem, wsu, red);
+  } else {
+    const int groups = (n + kPdGroup - 1) / kPdGroup;
+    if (u < groups) {
+      const int a0 = u * kPdGroup;
+      const int na = min(kPdGroup, n - a0);
+      if (na < 2) return;
+      pd_unit<Op, kPdGroup, 0, VEC, LDP>(s, a0, na, 0, 0, nelem, wsu, red);
+    } else {
+      int pair = (u - groups) >> 1, ga = 0;
+      const int half = (u - groups) & 1;
+      while (pair >= groups - 1 - ga) {
+        pair -= groups - 1 - ga;
+        ++ga;
+      }
+      const int gb = ga + 1 + pair;
+      const int b0 = gb * kPdGroup + half * kPdCross;
+      const int nb = min(kPdCross, n - b0);
+      if (nb < 1) return;
+      pd_unit<Op, kPdGroup, kPdCross, VEC, LDP>(s, ga * kPdGroup, kPdGroup, b0, nb, nelem, wsu, red);
+    }
+  }
+}
+
+// One wave per pair i < j (numbered row by row): the pair's partials of all
+// blocks, lane l adding blocks l, l + 64, ... in order, then the butterfly;
+// d2[i][j] and d2[j][i] get the same bits. accumulate: the sum is added to
+// d2[i][j] first. The diagonal is written (+0.0) unless accumulating.
+// cap: rows of the diagonal units (4 or 8).
+__global__ __launch_bounds__(kBlock) void k_pairdist_finish(const double* __restrict__ ws, unsigned blocks, int n,
+                                                            int cap, double* __restrict__ d2, int accumulate) {
+  if (blockIdx.x == 0 && threadIdx.x < static_cast<unsigned>(n) && !accumulate)
+    d2[static_cast<size_t>(threadIdx.x) * (n + 1)] = 0.0;
+  const int lane = threadIdx.x & 63;
+  int pair = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (pair >= n * (n - 1) / 2) return;
+  int i = 0;
+  while (pair >= n - 1 - i) {
+    pair -= n - 1 - i;
+    ++i;
+  }
+  const int j = i + 1 + pair;
+  const int groups = (n + kPdGroup - 1) / kPdGroup;
+  const int gi = i / kPdGroup, gj = j / kPdGroup, li = i % kPdGroup, lj = j % kPdGroup;
+  int unit, slot;
+  if (gi == gj) {
+    unit = groups > 1 ? gi : 0;
+    slot = pd_diag_slot(cap, li, lj);
+  } else {
+    unit = groups + 2 * (gi * groups - gi * (gi + 1) / 2 + (gj - gi - 1)) + lj / kPdCross;
+    slot = li * kPdCross + lj % kPdCross;
+  }
+  const double* const src = ws + (static_cast<size_t>(unit) * kPdSlots + slot) * blocks;
+  double v = 0.0;
+  for (unsigned b = lane; b < blocks; b += 64) v = v + src[b];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+  if (lane == 0) {
+    double* const pij = d2 + static_cast<size_t>(i) * n + j;
+    const double r = accumulate ? *pij + v : v;
+    *pij = r;
+    d2[static_cast<size_t>(j) * n + i] = r;
+  }
+}
+
+}  // namespace dlsim

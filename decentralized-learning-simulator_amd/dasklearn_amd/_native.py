@@ -63,6 +63,9 @@ EXPORTS = (
     "dlsim_sgd_momentum_step_tensors",
     "dlsim_robust_reduce",
     "dlsim_robust_reduce_tensors",
+    "dlsim_pairwise_sqdist",
+    "dlsim_pairwise_sqdist_tensors",
+    "dlsim_pairdist_geometry",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -198,6 +201,12 @@ def load() -> ctypes.CDLL:
         lib.dlsim_robust_reduce_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), ctypes.POINTER(sz),
                                                     i, i, vp, i, vp]
         lib.dlsim_robust_reduce_tensors.restype = i
+        lib.dlsim_pairwise_sqdist.argtypes = [ctypes.POINTER(vp), i, sz, i, vp, i, vp]
+        lib.dlsim_pairwise_sqdist.restype = i
+        lib.dlsim_pairwise_sqdist_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), i, vp, i, vp]
+        lib.dlsim_pairwise_sqdist_tensors.restype = i
+        lib.dlsim_pairdist_geometry.argtypes = [i, i, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint)]
+        lib.dlsim_pairdist_geometry.restype = i
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -506,6 +515,65 @@ def robust_reduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[i
                                               (ctypes.c_size_t * max(t, 1))(*numels),
                                               (ctypes.c_size_t * max(t, 1))(*out_offsets), int(lo), int(hi),
                                               out_base, dtype, stream_handle))
+
+
+MAX_PAIRDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_PAIRDIST_INPUTS
+
+
+def check_pairdist_fan_in(n: int) -> None:
+    """The distance kernels hold one accumulator per pair of a row group in registers."""
+    if n > MAX_PAIRDIST_INPUTS:
+        raise ValueError(f"the pairwise-distance kernels take at most {MAX_PAIRDIST_INPUTS} models (got {n})")
+
+
+def pairwise_sqdist(inputs, out, accumulate: bool = False, stream=None):
+    """dlsim_pairwise_sqdist: out[i][j] = sum_e (double(x_i[e]) - double(x_j[e]))^2
+    over n flat device tensors of one dtype (fp32, fp64, bf16, fp16) and size;
+    `out` is a contiguous float64 device tensor of n*n elements that shares no
+    memory with an input (the inputs may alias each other). accumulate: add to
+    what `out` holds (bitwise symmetric, diagonal +0.0, as a call without it
+    leaves it). Deterministic (no atomics). Stream-ordered."""
+    import torch
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_pairdist_fan_in(n)
+    if not out.is_cuda or out.dtype != torch.float64 or out.numel() != n * n or not out.is_contiguous():
+        raise ValueError(f"the distance matrix must be a contiguous float64 device tensor of {n * n} elements")
+    dt, numel = inputs[0].dtype, inputs[0].numel()
+    for t in inputs:
+        if not t.is_cuda or t.device != out.device:
+            raise ValueError("the pairwise distance needs device tensors on one device (no CPU path)")
+        if t.dtype != dt or t.numel() != numel or not t.is_contiguous():
+            raise ValueError("inputs must be contiguous, same dtype and size")
+    _check("dlsim_pairwise_sqdist",
+           load().dlsim_pairwise_sqdist((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, numel,
+                                        dtype_code(dt, single_task=True), out.data_ptr(), int(bool(accumulate)),
+                                        _stream_handle(out.device, stream)))
+    return out
+
+
+def pairwise_sqdist_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], dtype: int, out_ptr: int,
+                                accumulate: bool, stream_handle) -> None:
+    """dlsim_pairwise_sqdist_tensors on pointers the caller has already
+    validated (the arena path). in_ptrs model-major (tensor k of model i at
+    i * t + k); the n*n doubles at out_ptr."""
+    t = len(numels)
+    check_pairdist_fan_in(n)
+    _check("dlsim_pairwise_sqdist_tensors",
+           load().dlsim_pairwise_sqdist_tensors((ctypes.c_void_p * max(len(in_ptrs), 1))(*in_ptrs), n, t,
+                                                (ctypes.c_size_t * max(t, 1))(*numels), dtype, out_ptr,
+                                                int(bool(accumulate)), stream_handle))
+
+
+def pairdist_geometry(n: int, torch_dtype, numel: int):
+    """(tile elements, blocks) of dlsim_pairwise_sqdist for n 16-byte-aligned
+    inputs of numel elements (dlsim_pairdist_geometry; no GPU needed)."""
+    tile, blocks = ctypes.c_size_t(0), ctypes.c_uint(0)
+    _check("dlsim_pairdist_geometry",
+           load().dlsim_pairdist_geometry(n, dtype_code(torch_dtype, single_task=True), numel, ctypes.byref(tile),
+                                          ctypes.byref(blocks)))
+    return tile.value, blocks.value
 
 
 DLSIM_ALLOC_CONTIGUOUS = 1

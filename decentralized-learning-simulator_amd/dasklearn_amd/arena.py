@@ -1514,6 +1514,119 @@ def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Opti
     return _restride(out, layout) if staged else out
 
 
+def model_distances(models: List[nn.Module], device=None) -> torch.Tensor:
+    """The [n, n] float64 host matrix of squared L2 distances between the
+    models' parameters (dlsim_pairwise_sqdist): entry [i][j] is the sum over
+    every parameter element of (double(x_i) - double(x_j))^2, bitwise
+    symmetric, the diagonal +0.0. Parameters only, as the aggregators. The
+    dtype groups of models[0]'s layout add into the one matrix in layout
+    order. A model whose parameter list differs from models[0]'s raises
+    ValueError; more than 32 models too; an empty list IndexError.
+
+    The three input routes of robust_modules: device arenas are read in place,
+    separate device tensors go through dlsim_pairwise_sqdist_tensors, host
+    models are copied into one device row per model and dtype. The matrix
+    comes back with one D2H copy of n*n doubles, which waits for the stream."""
+    models[0]  # IndexError for an empty list, as the aggregators
+    n = len(models)
+    _native.check_pairdist_fan_in(n)
+    layout, all_params, in_views = input_arenas(models)  # ZipMismatch is a ValueError
+    dev = _target_device(all_params[0], device)
+    dix = dev.index
+    keep = []  # page-locked blocks and contiguous copies the queued work reads
+    with torch.no_grad(), torch.cuda.device(dev):
+        raw_stream = torch._C._cuda_getCurrentRawStream(dix)
+        d2 = torch.empty(n * n, dtype=torch.float64, device=dev)
+        first = True
+        for dt, idx in layout.groups.items():
+            total = layout.totals[dt]
+            if total == 0:
+                continue
+            views = in_views[dt]
+            if views is not None and all(v.get_device() == dix for v in views):
+                _native.pairwise_sqdist(views, d2, accumulate=not first)
+            elif all(ps[k].get_device() == dix for ps in all_params for k in idx):
+                copies, ptrs = _data_ptrs(all_params, idx)
+                keep.append(copies)
+                _native.pairwise_sqdist_tensors_raw(ptrs, n, layout.split_sizes[dt],
+                                                    _native.dtype_code(dt, single_task=True), d2.data_ptr(),
+                                                    not first, raw_stream)
+            else:
+                rows, pinned = _robust_rows(all_params, idx, total, dt, dev)
+                keep.append((rows, pinned))
+                _native.pairwise_sqdist(rows, d2, accumulate=not first)
+            first = False
+        if first:
+            d2.zero_()
+        host = d2.cpu()  # waits for the stream: the staged copies' sources may go now
+    del keep
+    return host.reshape(n, n)
+
+
+def _copy_of_params(model0: nn.Module, layout: ParamLayout, params, views, dev: torch.device,
+                    host_out: bool) -> nn.Module:
+    """copy.deepcopy(model0) whose parameters hold `params`' values bit for
+    bit (a plain copy, not a 1-way reduce: x*0 + 1*x is not the identity for
+    Inf and NaN), in one arena per dtype on the host or on `dev`. views[dt]:
+    the model's flat arena of that dtype (one copy), or None (one per tensor)."""
+    arenas = {}
+    with torch.no_grad():
+        for dt, idx in layout.groups.items():
+            total = layout.totals[dt]
+            flat = torch.empty(total, dtype=dt) if host_out else arena_empty(total, dt, dev)
+            if views[dt] is not None:
+                flat.copy_(views[dt])
+            else:
+                for k in idx:
+                    off = layout.offsets[k]
+                    p = params[k]
+                    flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
+            arenas[dt] = flat
+    return _restride(module_from_arenas(model0, layout, arenas), layout)
+
+
+def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Optional[bool] = None) -> nn.Module:
+    """Krum (m None) or Multi-Krum(m) of `models` with Byzantine count f
+    (gradient_aggregation/krum.py has the rule): the distance matrix on the
+    GPU (model_distances), the selection on the host, then Krum copies the
+    selected model's parameters bit for bit and Multi-Krum runs the selected
+    models, in ascending index order, through the exact weighted reduce with
+    float(1./m) each, as FedAvg.aggregate(selected) does. Buffers and
+    attributes are copy.deepcopy(models[0])'s; the result lives where
+    models[0] lives unless to_host says otherwise.
+
+    The selection needs the matrix on the host: one D2H copy of n*n doubles
+    and one stream synchronisation per call."""
+    from dasklearn_amd.gradient_aggregation import krum as _krum
+    model0 = models[0]  # IndexError for an empty list, as FedAvg
+    n = len(models)
+    _native.check_pairdist_fan_in(n)
+    _krum.check_krum_params(n, f, 1 if m is None else m)
+    d2 = model_distances(models)
+    chosen = _krum.krum_select(d2.tolist(), f, 1 if m is None else m)
+    p0 = module_params(model0)
+    host_out = (not any(p.is_cuda for p in p0)) if to_host is None else to_host
+    if m is None:
+        layout, all_params, in_views = input_arenas(models)
+        w = chosen[0]
+        views = {dt: None if v is None else v[w] for dt, v in in_views.items()}
+        return _copy_of_params(model0, layout, all_params[w], views, _target_device(all_params[0], None), host_out)
+    out = aggregate_modules([models[i] for i in chosen], None, _native.DLSIM_EXACT, to_host=host_out)
+    if chosen[0] == 0:
+        return out
+    # the reduce copied the first selected model's buffers and attributes:
+    # models[0]'s it must be, around the same parameters
+    memo = {}
+    for q0, q in zip(p0, module_params(out)):
+        q.requires_grad_(q0.requires_grad)
+        memo[id(q0)] = q
+    res = _clone_module(model0, memo)
+    entry = _arena_entry(out)
+    if entry is not None:
+        _register_arenas(res, entry)
+    return res
+
+
 def to_device_arena(model: nn.Module, device=None) -> nn.Module:
     """A copy of `model` (deepcopy semantics) whose parameters are views of one
     device arena per dtype — the form the aggregate reads in place. A plain

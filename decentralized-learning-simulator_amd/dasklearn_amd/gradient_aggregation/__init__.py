@@ -4,8 +4,9 @@
 selected through `SessionSettings.gradient_aggregation`,
 dasklearn/session_settings.py:40 and model_manager.py:37-39), so settings
 objects built for the reference select the HIP implementation unchanged.
-MEDIAN and TRIMMED_MEAN are new here (gradient_aggregation/robust.py): the
-reference has no such members.
+MEDIAN and TRIMMED_MEAN (gradient_aggregation/robust.py) and KRUM and
+MULTI_KRUM (gradient_aggregation/krum.py) are new here: the reference has no
+such members.
 """
 from abc import abstractmethod
 from enum import IntEnum
@@ -18,6 +19,8 @@ class GradientAggregationMethod(IntEnum):
     FEDAVG = 1
     MEDIAN = 2
     TRIMMED_MEAN = 3
+    KRUM = 4
+    MULTI_KRUM = 5
 
 
 class GradientAggregation:

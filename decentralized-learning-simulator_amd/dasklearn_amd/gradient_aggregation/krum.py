@@ -1,0 +1,141 @@
+"""Krum and Multi-Krum (Blanchard et al., 2017) on the MI355X: the fourth and
+fifth plugins behind `GradientAggregationMethod` (KRUM = 4, MULTI_KRUM = 5),
+and `model_distances`, the consensus distance between n models.
+
+The reference has one aggregator, FedAvg (dasklearn/gradient_aggregation/
+fedavg.py), and measures no distance between models; the coordinate-wise
+rules of robust.py judge every element on its own. Against a peer that sends a
+plausible-looking model that is wrong as a whole (scaled, sign-flipped,
+trained on poisoned labels) the standard defences are distance-based.
+
+The rule, for n models, a Byzantine count f >= 0 with n >= 2f + 3, and the
+matrix d2 of squared L2 distances between the models' parameters
+(`model_distances`: one HIP kernel per dtype group, csrc/pairdist_kernels.hpp,
+every term in double):
+
+    D[i][j]  = d2[i][j] if finite, else +Inf
+    score[i] = the n - f - 2 smallest D[i][j], j != i, added in ascending order
+    ranking  = by (score, index): ties and all-Inf scores go to the lower index
+
+A peer with a NaN or Inf parameter has an infinite score and is never chosen
+while enough finite peers remain. Krum returns the first-ranked model: its
+parameters are a plain copy of that model's, bit for bit. Multi-Krum(m),
+1 <= m <= n - f (default n - f), takes the m first-ranked models in ascending
+index order through the exact weighted reduce with float(1./m) each: its
+parameters equal FedAvg.aggregate(selected) bit for bit. Scores and selection
+are computed on the host in Python floats.
+
+As in every plugin here, buffers and attributes are copy.deepcopy(models[0])'s
+and the inputs are only read. Both are unweighted: `weights` of None or [] is
+accepted; a non-empty list of another length than the models raises
+AssertionError (as FedAvg), one of the right length ValueError. An empty model
+list raises IndexError; more than 32 models, or a model whose parameter list
+differs from models[0]'s, ValueError.
+
+Cost: the selection needs the matrix on the host, so every aggregate pays one
+D2H copy of n*n doubles and one stream synchronisation between the distance
+kernel and the copy or reduce that follows. A device-side selection is not
+implemented.
+"""
+import math
+from typing import List, Optional, Sequence
+
+from torch import nn
+
+from dasklearn_amd.arena import krum_modules, model_distances  # noqa: F401  (model_distances: public here)
+from dasklearn_amd.gradient_aggregation import GradientAggregation
+
+
+def _check_unweighted(name: str, models, weights) -> None:
+    if weights:
+        assert len(weights) == len(models)
+        raise ValueError(f"{name} is unweighted: pass weights=None (got {len(weights)} weights)")
+
+
+def check_krum_params(n: int, f: int, m: int = 1) -> None:
+    """ValueError unless f >= 0, n >= 2f + 3 and 1 <= m <= n - f."""
+    if f < 0 or n < 2 * f + 3:
+        raise ValueError(f"Krum over n = {n} models with f = {f} Byzantine ones: needs f >= 0 and n >= 2*f + 3")
+    if not 1 <= m <= n - f:
+        raise ValueError(f"Multi-Krum over n = {n} models with f = {f}: m = {m} must satisfy 1 <= m <= n - f")
+
+
+def krum_scores(d2: Sequence[Sequence[float]], f: int) -> List[float]:
+    """score[i] of the n x n matrix d2 (any nested sequence of floats): the
+    sum, in ascending order, of the n - f - 2 smallest entries of row i off the
+    diagonal, a non-finite entry counting as +Inf."""
+    n = len(d2)
+    f = int(f)
+    check_krum_params(n, f)
+    scores = []
+    for i in range(n):
+        row = sorted((float(d2[i][j]) if math.isfinite(d2[i][j]) else math.inf) for j in range(n) if j != i)
+        s = 0.0
+        for v in row[:n - f - 2]:
+            s += v
+        scores.append(s)
+    return scores
+
+
+def krum_select(d2: Sequence[Sequence[float]], f: int, m: int = 1) -> List[int]:
+    """The indices of the m models ranked first by (score, index), in
+    ascending index order."""
+    n = len(d2)
+    f, m = int(f), int(m)
+    check_krum_params(n, f, m)
+    scores = krum_scores(d2, f)
+    return sorted(sorted(range(n), key=lambda i: (scores[i], i))[:m])
+
+
+class Krum(GradientAggregation):
+    """The one model closest to its n - f - 2 nearest neighbours; f Byzantine
+    peers are tolerated among n >= 2f + 3."""
+
+    f = 1
+
+    @classmethod
+    def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
+                  to_host: Optional[bool] = None) -> nn.Module:
+        """to_host=None (default): the result lives where models[0] lives;
+        False keeps it on the GPU."""
+        _check_unweighted("Krum", models, weights)
+        return krum_modules(models, cls.f, None, to_host=to_host)
+
+    @classmethod
+    def with_params(cls, f: int, m: Optional[int] = None):
+        """A Krum class for Byzantine count f: the plugin signature
+        ModelManager calls. m is accepted for symmetry and must be None or 1."""
+        f = int(f)
+        if f < 0:
+            raise ValueError(f"f must be >= 0 (got {f})")
+        if m is not None and int(m) != 1:
+            raise ValueError(f"Krum selects one model (got m = {m}); MultiKrum takes m")
+        return type(f"Krum{f}", (cls,), {"f": f})
+
+
+class MultiKrum(GradientAggregation):
+    """The mean of the m first-ranked models (default m = n - f)."""
+
+    f = 1
+    m: Optional[int] = None
+
+    @classmethod
+    def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
+                  to_host: Optional[bool] = None) -> nn.Module:
+        _check_unweighted("MultiKrum", models, weights)
+        models[0]  # IndexError for an empty list, as FedAvg
+        m = len(models) - cls.f if cls.m is None else cls.m
+        return krum_modules(models, cls.f, m, to_host=to_host)
+
+    @classmethod
+    def with_params(cls, f: int, m: Optional[int] = None):
+        """A MultiKrum class for Byzantine count f that averages m models
+        (None: n - f of the n it is given)."""
+        f = int(f)
+        if f < 0:
+            raise ValueError(f"f must be >= 0 (got {f})")
+        if m is not None:
+            m = int(m)
+            if m < 1:
+                raise ValueError(f"m must be >= 1 (got {m})")
+        return type(f"MultiKrum{f}" + ("" if m is None else f"x{m}"), (cls,), {"f": f, "m": m})

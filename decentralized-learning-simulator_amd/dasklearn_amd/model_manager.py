@@ -4,8 +4,12 @@ Collects incoming models keyed by peer id (first one wins, :27-32) and
 aggregates them with the method chosen by `settings.gradient_aggregation`
 (:37-43): FEDAVG = 1 as in the reference, and the two robust aggregators it
 does not have, MEDIAN = 2 and TRIMMED_MEAN = 3 (the latter trims
-`settings.aggregation_trim` values, default 1, at each end). The `dataset` argument is accepted and ignored, as the reference's
-aggregate task passes None (functions.py:99).
+`settings.aggregation_trim` values, default 1, at each end), and the two
+distance-based ones, KRUM = 4 and MULTI_KRUM = 5 (Byzantine count
+`settings.aggregation_byzantine`, default 1; Multi-Krum averages
+`settings.aggregation_multi_krum_m` models, default None = n - f). The
+`dataset` argument is accepted and ignored, as the reference's aggregate task
+passes None (functions.py:99).
 """
 import logging
 from typing import Dict, List, Optional
@@ -14,6 +18,7 @@ import torch.nn as nn
 
 from dasklearn_amd.gradient_aggregation import GradientAggregationMethod
 from dasklearn_amd.gradient_aggregation.fedavg import FedAvg
+from dasklearn_amd.gradient_aggregation.krum import Krum, MultiKrum
 from dasklearn_amd.gradient_aggregation.robust import CoordinateMedian, TrimmedMean
 
 
@@ -41,6 +46,11 @@ class ModelManager:
             return CoordinateMedian
         if method == GradientAggregationMethod.TRIMMED_MEAN:
             return TrimmedMean.with_trim(getattr(self.settings, "aggregation_trim", 1))
+        if method == GradientAggregationMethod.KRUM:
+            return Krum.with_params(getattr(self.settings, "aggregation_byzantine", 1))
+        if method == GradientAggregationMethod.MULTI_KRUM:
+            return MultiKrum.with_params(getattr(self.settings, "aggregation_byzantine", 1),
+                                         getattr(self.settings, "aggregation_multi_krum_m", None))
         return None  # the reference returns None for unknown methods too
 
     def aggregate_trained_models(self, weights: List[float] = None) -> Optional[nn.Module]:

@@ -661,6 +661,75 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
                                 const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype, void* stream);
 
 /*
+ * dlsim_pairwise_sqdist: the matrix of squared L2 distances between n flat
+ * buffers, the primitive under Krum and Multi-Krum and the consensus distance
+ * of decentralized-learning papers.
+ *
+ * New: the reference has one aggregator, FedAvg
+ * (dasklearn/gradient_aggregation/fedavg.py:10-26), and measures no distance
+ * between models. This entry replaces no reference code. For i != j
+ *   d_d2[i*n + j] = sum over e of (double(x_i[e]) - double(x_j[e]))^2
+ * with every value widened to double (exact for all four dtypes), the
+ * subtraction in double and every term added with one double fma. The
+ * summation order is the implementation's and fixed: no atomics; per-block
+ * partial sums go to a stream-ordered workspace (hipMallocAsync /
+ * hipFreeAsync on `stream`) and a second small kernel adds them in block
+ * order. Grid and tile are a function of (n, dtype, n_elems, whether every
+ * input is 16-byte aligned) only, so two calls with the same arguments return
+ * the same bits. All terms are non-negative: a finite entry is within
+ * (n_elems + 8) * 2^-53 relative of the exact value; an entry is NaN iff some
+ * term is NaN (a NaN input, or Inf - Inf), +Inf iff some term is infinite and
+ * none NaN. d_d2[i*n + j] and d_d2[j*n + i] hold the same bits (computed once,
+ * stored twice); d_d2[i*n + i] = +0.0.
+ *   d_inputs    host array of n device pointers (n_elems elements of dtype
+ *               each). Inputs may alias each other: the same pointer twice is
+ *               distance 0.
+ *   n           1 <= n <= DLSIM_MAX_PAIRDIST_INPUTS; n == 1 writes the single 0
+ *   dtype       all four of enum dlsim_dtype
+ *   d_d2        device buffer of n*n doubles, row-major; it must share no byte
+ *               with an input
+ *   accumulate  0: d_d2 is written. 1: the result is added to what d_d2[i][j]
+ *               (i < j) holds and stored to both [i][j] and [j][i], the
+ *               diagonal is left alone: tensors and dtype groups combine into
+ *               one matrix this way. Inputs longer than one launch's 32-bit
+ *               byte offsets go as consecutive ranges, accumulated in order.
+ * n_elems == 0 writes zeros (accumulate 0) or nothing (accumulate 1), whatever
+ * the input pointers. Any alignment is accepted; 16-byte-aligned inputs take the vector path.
+ * Argument errors (DLSIM_E_ARG: null pointers, n out of range, accumulate not
+ * 0 or 1, d_d2 sharing a byte with an input; DLSIM_E_DTYPE) are decided before
+ * any HIP call. Stream-ordered.
+ */
+#define DLSIM_MAX_PAIRDIST_INPUTS 32
+int dlsim_pairwise_sqdist(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,
+                          void* stream);
+
+/*
+ * dlsim_pairwise_sqdist_tensors: dlsim_pairwise_sqdist over t separate tensors
+ * per model, summed into one matrix.
+ *   d_inputs   host array of n*t device pointers, model-major:
+ *              d_inputs[i*t + k] = tensor k of model i
+ *   n_elems    host array of t element counts
+ * Bit-identical to t dlsim_pairwise_sqdist calls in order, the first with the
+ * caller's `accumulate` and the rest with 1 (t == 0: zeros, or nothing when
+ * accumulating). Errors are decided for the whole list before the first
+ * launch. (New: it replaces no reference code.)
+ */
+int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems, int dtype,
+                                  double* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_pairdist_geometry — the tile (elements a block takes per step) and
+ * the first grid dimension dlsim_pairwise_sqdist uses for n 16-byte-aligned
+ * inputs of n_elems elements of dtype: block b takes the full tiles b,
+ * b + blocks, ..., the partial tile goes to block (full tiles) mod blocks and
+ * the elements past the last whole 16-byte vector to the last block.
+ * Misaligned inputs take tiles of 256 elements under the same rule. A
+ * diagnostic in the spirit of dlsim_kernel_name, for tests that aim at tile
+ * and grid edges; it touches no GPU. (New: no reference counterpart.)
+ */
+int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
