@@ -366,6 +366,53 @@ int check_pairdist_buffers(const void* const* in, size_t stride, int n, size_t b
   return DLSIM_OK;
 }
 
+// The fused reduce-and-measure dispatch (inst_reducedist.hip): arguments already checked.
+hipError_t reducedist_flat(const void* const* in, int n, const double* w, void* out, size_t nelem, int dtype,
+                           double* d2, int accumulate, hipStream_t st);
+void reducedist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
+
+// dtype, fan-in and flag of dlsim_wreduce_dist / _tensors
+int check_reducedist_scalars(int n, int dtype, int accumulate) {
+  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  if (n < 1) return fail(DLSIM_E_ARG, "n must be >= 1 (got %d)", n);
+  if (n > DLSIM_MAX_REDUCEDIST_INPUTS)
+    return fail(DLSIM_E_ARG, "n must be <= %d (got %d): the inputs' rows and accumulators are held in registers",
+                DLSIM_MAX_REDUCEDIST_INPUTS, n);
+  if (accumulate != 0 && accumulate != 1) return fail(DLSIM_E_ARG, "accumulate must be 0 or 1 (got %d)", accumulate);
+  return DLSIM_OK;
+}
+
+// The kernel uses the fp32 value of a weight unless the buffers are fp64: a
+// weight that the conversion would change is rejected, not rounded silently.
+int check_reducedist_weights(const double* w, int n, int dtype) {
+  if (!w) return fail(DLSIM_E_ARG, "null weights array");
+  if (dtype == DLSIM_F64) return DLSIM_OK;
+  for (int i = 0; i < n; ++i)
+    if (!(static_cast<double>(static_cast<float>(w[i])) == w[i]))
+      return fail(DLSIM_E_ARG, "weight %d (%.17g) is not representable in fp32", i, w[i]);
+  return DLSIM_OK;
+}
+
+// The n inputs of one tensor (stride apart in `in`) of `bytes` bytes each
+// against one output range (out null or out_bytes 0: none) and the distance vector:
+// no null input, no byte shared. The inputs may alias each other.
+int check_reducedist_buffers(const void* const* in, size_t stride, int n, size_t bytes, const void* out,
+                             size_t out_bytes, const double* d2) {
+  if (bytes == 0) return DLSIM_OK;
+  if (out_bytes == 0) out = nullptr;
+  const uintptr_t v0 = reinterpret_cast<uintptr_t>(d2), v1 = v0 + sizeof(double) * static_cast<size_t>(n);
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + out_bytes;
+  if (out && o0 < v1 && v0 < o1) return fail(DLSIM_E_ARG, "the distance vector overlaps the output");
+  for (int i = 0; i < n; ++i) {
+    const void* p = in[static_cast<size_t>(i) * stride];
+    if (!p) return fail(DLSIM_E_ARG, "null input pointer at index %d", i);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
+    if (a0 < v1 && v0 < a0 + bytes) return fail(DLSIM_E_ARG, "the distance vector overlaps input %d", i);
+    if (out && a0 < o1 && o0 < a0 + bytes) return fail(DLSIM_E_ARG, "output overlaps input %d", i);
+  }
+  return DLSIM_OK;
+}
+
 }  // namespace dlsim_host
 
 // the per-policy entries live in the inst_*.hip units
@@ -1259,6 +1306,73 @@ int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems
   if (rc != DLSIM_OK) return rc;
   if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
   pairdist_geometry(n, dtype, n_elems, tile_elems, blocks);
+  return DLSIM_OK;
+}
+
+int dlsim_wreduce_dist(const void* const* d_inputs, int n, const double* h_weights, void* d_out, size_t n_elems,
+                       int dtype, double* d_d2, int accumulate, void* stream) {
+  g_err.clear();
+  int rc = check_reducedist_scalars(n, dtype, accumulate);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
+  if (!d_d2) return fail(DLSIM_E_ARG, "null distance vector pointer");
+  rc = check_reducedist_weights(h_weights, n, dtype);
+  if (rc != DLSIM_OK) return rc;
+  rc = check_reducedist_buffers(d_inputs, 1, n, n_elems * elem_bytes(dtype), d_out, n_elems * elem_bytes(dtype), d_d2);
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = reducedist_flat(d_inputs, n, h_weights, d_out, n_elems, dtype, d_d2, accumulate,
+                                       static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "reduce-and-measure launch");
+}
+
+int dlsim_wreduce_dist_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                               const size_t* out_off_bytes, const double* h_weights, void* d_out, int dtype,
+                               double* d_d2, int accumulate, void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_reducedist_scalars(n, dtype, accumulate);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_d2) return fail(DLSIM_E_ARG, "null distance vector pointer");
+  rc = check_reducedist_weights(h_weights, n, dtype);
+  if (rc != DLSIM_OK) return rc;
+  if (t > 0 && (!d_inputs || !n_elems || (d_out && !out_off_bytes))) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  const size_t ts = static_cast<size_t>(t);
+  // Every tensor's output range against every input of every tensor (the
+  // tensors run as launches in order on one stream), the distance vector and
+  // the other outputs; all before the first launch.
+  for (int k = 0; k < t; ++k) {
+    const char* const ok = d_out ? static_cast<const char*>(d_out) + out_off_bytes[k] : nullptr;
+    for (int j = 0; j < t; ++j) {
+      rc = check_reducedist_buffers(d_inputs + j, ts, n, n_elems[j] * esz, ok, n_elems[k] * esz, d_d2);
+      if (rc != DLSIM_OK) return fail(rc, "output of tensor %d, inputs of tensor %d: %s", k, j, std::string(g_err).c_str());
+      if (!ok || j == k || n_elems[k] == 0 || n_elems[j] == 0) continue;
+      const uintptr_t o0 = reinterpret_cast<uintptr_t>(ok), o1 = o0 + n_elems[k] * esz;
+      const uintptr_t q0 = reinterpret_cast<uintptr_t>(d_out) + out_off_bytes[j];
+      if (q0 < o1 && o0 < q0 + n_elems[j] * esz) return fail(DLSIM_E_ARG, "outputs of tensors %d and %d overlap", k, j);
+    }
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (t == 0) {
+    const hipError_t e = reducedist_flat(nullptr, n, h_weights, nullptr, 0, dtype, d_d2, accumulate, st);
+    return e == hipSuccess ? DLSIM_OK : hip_fail(e, "reduce-and-measure launch");
+  }
+  const void* row[DLSIM_MAX_REDUCEDIST_INPUTS];
+  for (int k = 0; k < t; ++k) {
+    for (int i = 0; i < n; ++i) row[i] = d_inputs[static_cast<size_t>(i) * ts + k];
+    void* const ok = d_out ? static_cast<char*>(d_out) + out_off_bytes[k] : nullptr;
+    const hipError_t e = reducedist_flat(row, n, h_weights, ok, n_elems[k], dtype, d_d2, k == 0 ? accumulate : 1, st);
+    if (e != hipSuccess) return hip_fail(e, "reduce-and-measure launch");
+  }
+  return DLSIM_OK;
+}
+
+int dlsim_reducedist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks) {
+  g_err.clear();
+  const int rc = check_reducedist_scalars(n, dtype, 0);
+  if (rc != DLSIM_OK) return rc;
+  if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
+  reducedist_geometry(n, dtype, n_elems, tile_elems, blocks);
   return DLSIM_OK;
 }
 

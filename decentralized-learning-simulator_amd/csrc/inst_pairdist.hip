@@ -81,7 +81,7 @@ hipError_t pd_run(const void* const* in, int n, size_t nelem, double* d2, int ac
     else pd_launch_main<Op, false>(g, s, n, len, static_cast<double*>(ws), st);
     e = hipGetLastError();
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(dlsim::k_pairdist_finish, dim3(fin_blocks), dim3(dlsim::kBlock), 0, st,
+      hipLaunchKernelGGL(dlsim::k_pairdist_finish<>, dim3(fin_blocks), dim3(dlsim::kBlock), 0, st,
                          static_cast<const double*>(ws), g.blocks, n, g.cap, d2, (accumulate || o > 0) ? 1 : 0);
       e = hipGetLastError();
     }

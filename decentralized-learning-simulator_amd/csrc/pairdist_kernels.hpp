@@ -180,6 +180,39 @@ __device__ __forceinline__ void pd_tile(const PdSlots& s, int a0, int na, int b0
   }
 }
 
+// A block's end: per accumulator the 64 lanes of a wave (xor butterfly), the
+// four waves through LDS in wave order, one store of the block's partial to
+// ws[k * gridDim.x + blockIdx.x]. (Shared with reducedist_kernels.hpp.)
+template <int NP>
+__device__ __forceinline__ void pd_block_sum(const double (&acc)[NP], double* __restrict__ ws,
+                                             double (*red)[kPdSlots]) {
+  static_assert(NP <= kPdSlots, "a block's partials fit its slots");
+  const size_t nblk = gridDim.x, b = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    const int k = threadIdx.x;
+    ws[static_cast<size_t>(k) * nblk + b] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// One wave's sum of the `blocks` partials at src: lane l adds blocks l,
+// l + 64, ... in order, then the butterfly; every lane returns the sum.
+__device__ __forceinline__ double pd_finish_sum(const double* __restrict__ src, unsigned blocks, int lane) {
+  double v = 0.0;
+  for (unsigned b = lane; b < blocks; b += 64) v = v + src[b];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+  return v;
+}
+
 // One unit of one block: rows a0 .. a0 + na (and b0 .. b0 + nb of a cross
 // unit) over this block's share of the items, then the block's partial sums
 // to ws[slot * gridDim.x + blockIdx.x]. Every block of a unit stores all its
@@ -206,19 +239,7 @@ __device__ __forceinline__ void pd_unit(const PdSlots& s, int a0, int na, int b0
     if (items * EV < nelem && b == nblk - 1)
       pd_tile<Op, RA, RB, false, true, 0>(s, a0, na, b0, nb, items * EV + threadIdx.x, nelem, acc);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NP) {
-    const int k = threadIdx.x;
-    ws[static_cast<size_t>(k) * nblk + b] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
+  pd_block_sum<NP>(acc, ws, red);
 }
 
 // grid (blocks, units). CROSS = false: the one diagonal unit of n <= CAP rows
@@ -263,7 +284,9 @@ __global__ __launch_bounds__(kBlock) void k_pairdist(const PdSlots s, int n, siz
 // blocks, lane l adding blocks l, l + 64, ... in order, then the butterfly;
 // d2[i][j] and d2[j][i] get the same bits. accumulate: the sum is added to
 // d2[i][j] first. The diagonal is written (+0.0) unless accumulating.
-// cap: rows of the diagonal units (4 or 8).
+// cap: rows of the diagonal units (4 or 8). (A template so that the header,
+// included by two units, defines it once: launched as k_pairdist_finish<>.)
+template <class = void>
 __global__ __launch_bounds__(kBlock) void k_pairdist_finish(const double* __restrict__ ws, unsigned blocks, int n,
                                                             int cap, double* __restrict__ d2, int accumulate) {
   if (blockIdx.x == 0 && threadIdx.x < static_cast<unsigned>(n) && !accumulate)
@@ -288,10 +311,7 @@ __global__ __launch_bounds__(kBlock) void k_pairdist_finish(const double* __rest
     slot = li * kPdCross + lj % kPdCross;
   }
   const double* const src = ws + (static_cast<size_t>(unit) * kPdSlots + slot) * blocks;
-  double v = 0.0;
-  for (unsigned b = lane; b < blocks; b += 64) v = v + src[b];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+  const double v = pd_finish_sum(src, blocks, lane);
   if (lane == 0) {
     double* const pij = d2 + static_cast<size_t>(i) * n + j;
     const double r = accumulate ? *pij + v : v;

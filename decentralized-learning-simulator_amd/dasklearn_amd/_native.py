@@ -66,6 +66,9 @@ EXPORTS = (
     "dlsim_pairwise_sqdist",
     "dlsim_pairwise_sqdist_tensors",
     "dlsim_pairdist_geometry",
+    "dlsim_wreduce_dist",
+    "dlsim_wreduce_dist_tensors",
+    "dlsim_reducedist_geometry",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -207,6 +210,14 @@ def load() -> ctypes.CDLL:
         lib.dlsim_pairwise_sqdist_tensors.restype = i
         lib.dlsim_pairdist_geometry.argtypes = [i, i, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint)]
         lib.dlsim_pairdist_geometry.restype = i
+        dp = ctypes.POINTER(ctypes.c_double)
+        lib.dlsim_wreduce_dist.argtypes = [ctypes.POINTER(vp), i, dp, vp, sz, i, vp, i, vp]
+        lib.dlsim_wreduce_dist.restype = i
+        lib.dlsim_wreduce_dist_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), ctypes.POINTER(sz),
+                                                   dp, vp, i, vp, i, vp]
+        lib.dlsim_wreduce_dist_tensors.restype = i
+        lib.dlsim_reducedist_geometry.argtypes = [i, i, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint)]
+        lib.dlsim_reducedist_geometry.restype = i
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -573,6 +584,73 @@ def pairdist_geometry(n: int, torch_dtype, numel: int):
     _check("dlsim_pairdist_geometry",
            load().dlsim_pairdist_geometry(n, dtype_code(torch_dtype, single_task=True), numel, ctypes.byref(tile),
                                           ctypes.byref(blocks)))
+    return tile.value, blocks.value
+
+
+MAX_REDUCEDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_REDUCEDIST_INPUTS
+
+
+def check_reducedist_fan_in(n: int) -> None:
+    """The fused kernels hold every input's row and accumulator in registers."""
+    if n > MAX_REDUCEDIST_INPUTS:
+        raise ValueError(f"the reduce-and-measure kernels take at most {MAX_REDUCEDIST_INPUTS} models (got {n})")
+
+
+def wreduce_dist(inputs, weights: Sequence[float], out, d2, accumulate: bool = False, stream=None):
+    """dlsim_wreduce_dist: `out` = the exact weighted reduce of n flat device
+    tensors of one dtype (fp32, fp64, bf16, fp16) and size, bit for bit what
+    wreduce gives, and d2[i] = sum_e (double(x_i[e]) - double(out[e]))^2 from
+    the same pass. `weights`: n Python floats (fp32-representable unless the
+    tensors are fp64). `out` may be None (distances only); it and `d2` (a
+    contiguous float64 device tensor of n elements) share no memory with an
+    input or each other. accumulate: add to what `d2` holds. Deterministic (no
+    atomics). Stream-ordered."""
+    import torch
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_reducedist_fan_in(n)
+    assert len(weights) == n
+    if not d2.is_cuda or d2.dtype != torch.float64 or d2.numel() != n or not d2.is_contiguous():
+        raise ValueError(f"the distance vector must be a contiguous float64 device tensor of {n} elements")
+    dt, numel = inputs[0].dtype, inputs[0].numel()
+    for t in list(inputs) + ([] if out is None else [out]):
+        if not t.is_cuda or t.device != d2.device:
+            raise ValueError("the reduce-and-measure needs device tensors on one device (no CPU path)")
+        if t.dtype != dt or t.numel() != numel or not t.is_contiguous():
+            raise ValueError("inputs and output must be contiguous, same dtype and size")
+    _check("dlsim_wreduce_dist",
+           load().dlsim_wreduce_dist((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n,
+                                     (ctypes.c_double * n)(*[float(w) for w in weights]),
+                                     None if out is None else out.data_ptr(), numel,
+                                     dtype_code(dt, single_task=True), d2.data_ptr(), int(bool(accumulate)),
+                                     _stream_handle(d2.device, stream)))
+    return out, d2
+
+
+def wreduce_dist_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], out_offsets: Sequence[int],
+                             weights: Sequence[float], out_base: Optional[int], dtype: int, d2_ptr: int,
+                             accumulate: bool, stream_handle) -> None:
+    """dlsim_wreduce_dist_tensors on pointers the caller has already validated
+    (the arena path). in_ptrs model-major (tensor k of model i at i * t + k);
+    output tensor k at out_base + out_offsets[k] bytes; n doubles at d2_ptr."""
+    t = len(numels)
+    check_reducedist_fan_in(n)
+    _check("dlsim_wreduce_dist_tensors",
+           load().dlsim_wreduce_dist_tensors((ctypes.c_void_p * max(len(in_ptrs), 1))(*in_ptrs), n, t,
+                                             (ctypes.c_size_t * max(t, 1))(*numels),
+                                             (ctypes.c_size_t * max(t, 1))(*out_offsets),
+                                             (ctypes.c_double * n)(*[float(w) for w in weights]), out_base, dtype,
+                                             d2_ptr, int(bool(accumulate)), stream_handle))
+
+
+def reducedist_geometry(n: int, torch_dtype, numel: int):
+    """(tile elements, blocks) of dlsim_wreduce_dist for n 16-byte-aligned
+    inputs of numel elements (dlsim_reducedist_geometry; no GPU needed)."""
+    tile, blocks = ctypes.c_size_t(0), ctypes.c_uint(0)
+    _check("dlsim_reducedist_geometry",
+           load().dlsim_reducedist_geometry(n, dtype_code(torch_dtype, single_task=True), numel, ctypes.byref(tile),
+                                            ctypes.byref(blocks)))
     return tile.value, blocks.value
 
 

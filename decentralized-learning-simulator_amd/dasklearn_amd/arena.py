@@ -1563,6 +1563,134 @@ def model_distances(models: List[nn.Module], device=None) -> torch.Tensor:
     return host.reshape(n, n)
 
 
+class ReduceDistPlan:
+    """The inputs of the fused reduce-and-measure kernel (dlsim_wreduce_dist)
+    for a list of models, resolved once and run any number of times: the
+    iterations of the geometric median and of centered clipping
+    (gradient_aggregation/geomed.py) read the same rows with new weights.
+
+    The three input routes of robust_modules / model_distances, per dtype
+    group: device arenas are read in place, separate device tensors go through
+    dlsim_wreduce_dist_tensors, host models are copied into one device row per
+    model and dtype (once, here). A model whose parameter list differs from
+    models[0]'s raises ValueError, more than 32 models too, an empty list
+    IndexError."""
+
+    def __init__(self, models: List[nn.Module], device=None):
+        self.model0 = models[0]  # IndexError for an empty list, as FedAvg
+        n = self.n = len(models)
+        _native.check_reducedist_fan_in(n)
+        layout, all_params, in_views = input_arenas(models)  # ZipMismatch is a ValueError
+        self.layout = layout
+        self.dev = dev = _target_device(all_params[0], device)
+        dix = dev.index
+        self.keep = []  # page-locked blocks and contiguous copies the queued work reads
+        self.staged = False
+        # per dtype: ("flat", one flat tensor per model) or ("tensors", one pointer list per model)
+        self.routes = {}
+        with torch.no_grad(), torch.cuda.device(dev):
+            for dt, idx in layout.groups.items():
+                total = layout.totals[dt]
+                if total == 0:
+                    continue
+                views = in_views[dt]
+                if views is not None and all(v.get_device() == dix for v in views):
+                    self.routes[dt] = ("flat", list(views))
+                elif all(ps[k].get_device() == dix for ps in all_params for k in idx):
+                    copies, ptrs = _data_ptrs(all_params, idx)
+                    self.keep.append(copies)
+                    self.staged = self.staged or bool(copies)
+                    t = len(idx)
+                    ptrs = list(ptrs)
+                    self.routes[dt] = ("tensors", [ptrs[i * t:(i + 1) * t] for i in range(n)])
+                else:
+                    rows, pinned = _robust_rows(all_params, idx, total, dt, dev)
+                    self.keep.append(pinned)
+                    self.staged = True
+                    self.routes[dt] = ("flat", rows)
+
+    def host_out(self, to_host: Optional[bool]) -> bool:
+        return (not any(p.is_cuda for p in self.layout.params)) if to_host is None else to_host
+
+    def run(self, idx: Sequence[int], weights: Sequence[float], center=None, want_out: bool = True):
+        """One pass over the models `idx` (behind `center`, a dict of flat
+        device arenas per dtype as an earlier pass returned it, as input 0 when
+        given) with one weight per input. Returns (dict dtype -> new device
+        arena, or {} without want_out; the float64 device vector of squared
+        distances, one per input). Dtype groups accumulate into the one vector
+        in layout order. Stream-ordered: nothing waits."""
+        layout, dev = self.layout, self.dev
+        idx = list(idx)
+        m = len(idx) + (center is not None)
+        assert len(weights) == m
+        outs: Dict[torch.dtype, torch.Tensor] = {}
+        with torch.no_grad(), torch.cuda.device(dev):
+            raw_stream = torch._C._cuda_getCurrentRawStream(dev.index)
+            d2 = torch.empty(m, dtype=torch.float64, device=dev)
+            first = True
+            for dt in layout.groups:
+                total = layout.totals[dt]
+                if total == 0:
+                    if want_out:
+                        outs[dt] = torch.empty(0, dtype=dt, device=dev)
+                    continue
+                out = arena_empty(total, dt, dev) if want_out else None
+                if want_out:
+                    outs[dt] = out
+                kind, data = self.routes[dt]
+                if kind == "flat":
+                    ins = ([center[dt]] if center is not None else []) + [data[i] for i in idx]
+                    _native.wreduce_dist(ins, weights, out, d2, accumulate=not first)
+                else:
+                    ptrs = []
+                    if center is not None:
+                        base = center[dt].data_ptr()
+                        ptrs += [base + o for o in layout.byte_offsets[dt]]
+                    for i in idx:
+                        ptrs += data[i]
+                    _native.wreduce_dist_tensors_raw(ptrs, m, layout.split_sizes[dt], layout.byte_offsets[dt],
+                                                     weights, None if out is None else out.data_ptr(),
+                                                     _native.dtype_code(dt, single_task=True), d2.data_ptr(),
+                                                     not first, raw_stream)
+                first = False
+            if first:
+                d2.zero_()
+        return outs, d2
+
+    def module(self, outs, to_host: Optional[bool]) -> nn.Module:
+        """copy.deepcopy(models[0]) around the arenas `outs` of a pass, on the
+        host when models[0] lives there (or to_host says so)."""
+        if self.host_out(to_host):
+            outs = arenas_to_host(outs, torch.cuda.current_stream(self.dev))  # waits for the stream
+        out = module_from_arenas(self.model0, self.layout, outs)
+        return _restride(out, self.layout) if self.staged else out
+
+
+def fp32_rounded(weights: Sequence[float]) -> List[float]:
+    """Every weight as the Python float of its fp32 rounding: what the fused
+    kernel is handed, for fp64 models too (trajectories are then reproducible
+    across dtypes)."""
+    return [float(np.float32(w)) for w in weights]
+
+
+def reduce_with_distances(models: List[nn.Module], weights: Sequence[float], device=None,
+                          to_host: Optional[bool] = None):
+    """(module, d2): the exact weighted reduce of `models` with `weights`
+    (rounded to fp32 first), as FedAvg.aggregate computes it, and the float64
+    host tensor of every model's squared L2 distance to that result over all
+    parameters: d2[i] = sum_e (double(x_i[e]) - double(out[e]))^2, from the
+    same pass over the models (dlsim_wreduce_dist). Buffers and
+    attributes are copy.deepcopy(models[0])'s; the module lives where models[0]
+    lives unless to_host says otherwise. The distances come back with one D2H
+    copy of n doubles, which waits for the stream."""
+    models[0]  # IndexError for an empty list, as the aggregators
+    assert len(weights) == len(models)
+    plan = ReduceDistPlan(models, device)
+    outs, d2 = plan.run(range(plan.n), fp32_rounded(weights))
+    host = d2.cpu()  # waits for the stream: the staged copies' sources may go now
+    return plan.module(outs, to_host), host
+
+
 def _copy_of_params(model0: nn.Module, layout: ParamLayout, params, views, dev: torch.device,
                     host_out: bool) -> nn.Module:
     """copy.deepcopy(model0) whose parameters hold `params`' values bit for

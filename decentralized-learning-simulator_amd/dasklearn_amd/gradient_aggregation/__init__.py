@@ -4,9 +4,10 @@
 selected through `SessionSettings.gradient_aggregation`,
 dasklearn/session_settings.py:40 and model_manager.py:37-39), so settings
 objects built for the reference select the HIP implementation unchanged.
-MEDIAN and TRIMMED_MEAN (gradient_aggregation/robust.py) and KRUM and
-MULTI_KRUM (gradient_aggregation/krum.py) are new here: the reference has no
-such members.
+MEDIAN and TRIMMED_MEAN (gradient_aggregation/robust.py), KRUM and MULTI_KRUM
+(gradient_aggregation/krum.py) and GEOMETRIC_MEDIAN and CENTERED_CLIP
+(gradient_aggregation/geomed.py) are new here: the reference has no such
+members.
 """
 from abc import abstractmethod
 from enum import IntEnum
@@ -21,6 +22,8 @@ class GradientAggregationMethod(IntEnum):
     TRIMMED_MEAN = 3
     KRUM = 4
     MULTI_KRUM = 5
+    GEOMETRIC_MEDIAN = 6
+    CENTERED_CLIP = 7
 
 
 class GradientAggregation:

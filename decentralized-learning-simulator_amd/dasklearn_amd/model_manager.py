@@ -7,7 +7,13 @@ does not have, MEDIAN = 2 and TRIMMED_MEAN = 3 (the latter trims
 `settings.aggregation_trim` values, default 1, at each end), and the two
 distance-based ones, KRUM = 4 and MULTI_KRUM = 5 (Byzantine count
 `settings.aggregation_byzantine`, default 1; Multi-Krum averages
-`settings.aggregation_multi_krum_m` models, default None = n - f). The
+`settings.aggregation_multi_krum_m` models, default None = n - f), and the
+two that keep every honest peer, GEOMETRIC_MEDIAN = 6
+(`settings.aggregation_gm_iters` Weiszfeld iterations, default 3, smoothing
+`settings.aggregation_gm_nu`, default 1e-6) and CENTERED_CLIP = 7
+(`settings.aggregation_clip_tau`, default None = the lower median of the
+distances, `settings.aggregation_clip_iters`, default 3). These four defaults
+are a choice, not measured. The
 `dataset` argument is accepted and ignored, as the reference's aggregate task
 passes None (functions.py:99).
 """
@@ -18,6 +24,7 @@ import torch.nn as nn
 
 from dasklearn_amd.gradient_aggregation import GradientAggregationMethod
 from dasklearn_amd.gradient_aggregation.fedavg import FedAvg
+from dasklearn_amd.gradient_aggregation.geomed import CenteredClip, GeometricMedian
 from dasklearn_amd.gradient_aggregation.krum import Krum, MultiKrum
 from dasklearn_amd.gradient_aggregation.robust import CoordinateMedian, TrimmedMean
 
@@ -51,6 +58,12 @@ class ModelManager:
         if method == GradientAggregationMethod.MULTI_KRUM:
             return MultiKrum.with_params(getattr(self.settings, "aggregation_byzantine", 1),
                                          getattr(self.settings, "aggregation_multi_krum_m", None))
+        if method == GradientAggregationMethod.GEOMETRIC_MEDIAN:
+            return GeometricMedian.with_params(getattr(self.settings, "aggregation_gm_iters", 3),
+                                               getattr(self.settings, "aggregation_gm_nu", 1e-6))
+        if method == GradientAggregationMethod.CENTERED_CLIP:
+            return CenteredClip.with_params(getattr(self.settings, "aggregation_clip_tau", None),
+                                            getattr(self.settings, "aggregation_clip_iters", 3))
         return None  # the reference returns None for unknown methods too
 
     def aggregate_trained_models(self, weights: List[float] = None) -> Optional[nn.Module]:

@@ -730,6 +730,91 @@ int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, con
 int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
 
 /*
+ * dlsim_wreduce_dist: "reduce and measure", the exact weighted reduce of n
+ * flat buffers and, from the same pass over them, every input's squared L2
+ * distance to the reduce's own output. The primitive under the geometric
+ * median (smoothed Weiszfeld) and centered clipping, and the consensus
+ * distance to the weighted mean of decentralized-learning papers.
+ *
+ * New: the reference has one aggregator, FedAvg
+ * (dasklearn/gradient_aggregation/fedavg.py:10-26), and measures no distance.
+ * This entry replaces no reference code.
+ *   d_out[e] = the bits dlsim_wreduce / dlsim_wreduce_f64 give in DLSIM_EXACT
+ *              mode for the same arguments: acc = x_0[e] * 0, then
+ *              acc = fl(acc + fl(w_i * x_i[e])) in input order, no contraction,
+ *              per-step rounding for the 2-byte dtypes
+ *   d_d2[i]  = sum over e of (double(x_i[e]) - double(d_out[e]))^2
+ * with d_out[e] the stored, rounded value, every value widened to double
+ * (exact for all four dtypes), the subtraction in double and every term added
+ * with one double fma. The summation order is the implementation's and fixed:
+ * no atomics; per-block partial sums go to a stream-ordered workspace
+ * (hipMallocAsync / hipFreeAsync on `stream`) and a second small kernel adds
+ * them in block order. Grid and tile are a function of (n, dtype, n_elems,
+ * whether every base is 16-byte aligned) only, so two calls with the same
+ * arguments return the same bits. All terms are non-negative: a finite entry
+ * is within (n_elems + 8) * 2^-53 relative of the exact value; an entry is NaN
+ * iff some term is NaN, +Inf iff some term is infinite and none NaN.
+ *   d_inputs    host array of n device pointers (n_elems elements of dtype
+ *               each). Inputs may alias each other.
+ *   n           1 <= n <= DLSIM_MAX_REDUCEDIST_INPUTS. n == 1 with weight 1.0
+ *               returns a finite row bit for bit with d_d2[0] = +0.0, and a
+ *               non-finite d_d2[0] for any other row.
+ *   h_weights   host array of n doubles. For DLSIM_F64 they are used as they
+ *               are; for the other dtypes the kernel uses the fp32 value and
+ *               each must survive (double)(float)w == w (DLSIM_E_ARG).
+ *   d_out       n_elems elements of dtype, sharing no byte with any input
+ *               (not even d_out == d_inputs[i]); or null: only the distances
+ *               are produced and nothing is stored
+ *   dtype       all four of enum dlsim_dtype
+ *   d_d2        device buffer of n doubles; it must share no byte with an
+ *               input or with d_out
+ *   accumulate  0: d_d2 is written. 1: the result is added to what d_d2[i]
+ *               holds: tensors and dtype groups combine into one vector this
+ *               way. Ranges longer than one launch's 32-bit byte offsets go as
+ *               consecutive pieces, accumulated in order.
+ * n_elems == 0 writes zeros (accumulate 0) or nothing (accumulate 1), whatever
+ * the pointers. Any alignment is accepted; 16-byte-aligned bases take the
+ * vector path, anything else a scalar form. Argument errors (DLSIM_E_ARG: null
+ * pointers, n out of range, a weight not representable, accumulate not 0 or 1,
+ * a forbidden overlap; DLSIM_E_DTYPE) are decided before any HIP call.
+ * Stream-ordered.
+ */
+#define DLSIM_MAX_REDUCEDIST_INPUTS 32
+int dlsim_wreduce_dist(const void* const* d_inputs, int n, const double* h_weights, void* d_out, size_t n_elems,
+                       int dtype, double* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_wreduce_dist_tensors: dlsim_wreduce_dist over t separate tensors per
+ * model, the distances summed into one vector.
+ *   d_inputs       host array of n*t device pointers, model-major:
+ *                  d_inputs[i*t + k] = tensor k of model i
+ *   n_elems        host array of t element counts
+ *   out_off_bytes  host array of t byte offsets into d_out (unused when d_out
+ *                  is null)
+ * Bit-identical to t dlsim_wreduce_dist calls in order, the first with the
+ * caller's `accumulate` and the rest with 1 (t == 0: zeros, or nothing when
+ * accumulating). No output range may share a byte with any input of any
+ * tensor, with the distance vector or with another output range; errors are
+ * decided for the whole list before the first launch. (New: it replaces no
+ * reference code.)
+ */
+int dlsim_wreduce_dist_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                               const size_t* out_off_bytes, const double* h_weights, void* d_out, int dtype,
+                               double* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_reducedist_geometry — the tile (elements a block takes per step) and
+ * the grid dlsim_wreduce_dist uses for n 16-byte-aligned buffers of n_elems
+ * elements of dtype, under the dealing rule of dlsim_pairdist_geometry: block
+ * b takes the full tiles b, b + blocks, ..., the partial tile goes to block
+ * (full tiles) mod blocks and the elements past the last whole vector to the
+ * last block. A lane takes 16 bytes of each row for n <= 8, 8 for n <= 16 and
+ * 4 (fp64: 8) above; misaligned buffers take tiles of 256 elements under the
+ * same rule. It touches no GPU. (New: no reference counterpart.)
+ */
+int dlsim_reducedist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
