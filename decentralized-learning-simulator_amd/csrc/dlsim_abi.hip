@@ -18,6 +18,7 @@
 
 #include "abi_common.hpp"
 #include "dispatch.hpp"
+#include "fanin_checks.hpp"
 
 // Every DLSIM_* switch named below is an A/B switch, read through
 // dlsim::ab_getenv: only when DLSIM_AB=1 is set as well (ab_env.hpp).
@@ -305,81 +306,48 @@ bool sgdm_cross_overlap(int t, const void* const* p, const void* const* g, const
   return false;
 }
 
-// The order-statistic reduce's dispatch (inst_robust.hip): arguments already checked.
+// The dispatches of the entries over n <= 32 inputs (inst_robust.hip,
+// inst_pairdist.hip, inst_reducedist.hip): arguments already checked.
 hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
                        hipStream_t st);
+hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
+                         hipStream_t st);
+void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
+hipError_t reducedist_flat(const void* const* in, int n, const double* w, void* out, size_t nelem, int dtype,
+                           double* d2, int accumulate, hipStream_t st);
+void reducedist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
 
-// dtype, fan-in and window of dlsim_robust_reduce / _tensors
-int check_robust_window(int n, int lo, int hi, int dtype) {
-  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
-  if (n < 1) return fail(DLSIM_E_ARG, "n must be >= 1 (got %d)", n);
-  if (n > DLSIM_MAX_ROBUST_INPUTS)
-    return fail(DLSIM_E_ARG, "n must be <= %d (got %d): the sorting network is held in registers",
-                DLSIM_MAX_ROBUST_INPUTS, n);
+// why each family stops at its DLSIM_MAX_*_INPUTS (check_fan_in, fanin_checks.hpp)
+constexpr const char* kRobustLimit = "the sorting network is held in registers";
+constexpr const char* kPairdistLimit = "the pairs' accumulators are held in registers";
+constexpr const char* kReducedistLimit = "the inputs' rows and accumulators are held in registers";
+
+// the order-statistic window of dlsim_robust_reduce / _tensors
+int check_robust_window(int n, int lo, int hi) {
   if (!(0 <= lo && lo < hi && hi <= n))
     return fail(DLSIM_E_ARG, "the window must satisfy 0 <= lo < hi <= n (got lo %d, hi %d, n %d)", lo, hi, n);
   return DLSIM_OK;
 }
 
-// One output range against its n inputs: any shared byte is rejected (exact
-// aliasing too: unlike the weighted reduce this is not declared in place).
-int check_robust_buffers(const void* const* in, size_t stride, int n, const void* out, size_t bytes) {
-  if (!out) return fail(DLSIM_E_ARG, "null output pointer");
-  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + bytes;
-  for (int i = 0; i < n; ++i) {
-    const void* p = in[static_cast<size_t>(i) * stride];
-    if (!p) return fail(DLSIM_E_ARG, "null input pointer at index %d", i);
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
-    if (a0 < o1 && o0 < a0 + bytes) return fail(DLSIM_E_ARG, "output overlaps input %d", i);
+inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// Every tensor's output range (d_out + offs[k]) against every input of every
+// tensor (the tensors run as launches in order on one stream), then against
+// the other outputs; all before the first launch. Empty tensors share nothing.
+int check_tensor_outputs(const void* const* in, int n, int t, const size_t* n_elems, const void* d_out,
+                         const size_t* offs, size_t esz) {
+  for (int k = 0; k < t; ++k) {
+    if (n_elems[k] == 0) continue;
+    if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+    const uintptr_t o0 = addr(d_out) + offs[k];
+    for (int j = 0; j < t; ++j) {
+      const int rc = check_inputs_apart(in + j, static_cast<size_t>(t), n, n_elems[j] * esz, o0, o0 + n_elems[k] * esz,
+                                        "output");
+      if (rc != DLSIM_OK)
+        return fail(rc, "output of tensor %d, inputs of tensor %d: %s", k, j, std::string(g_err).c_str());
+    }
   }
-  return DLSIM_OK;
-}
-
-// The pairwise squared-distance dispatch (inst_pairdist.hip): arguments already checked.
-hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
-                         hipStream_t st);
-void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
-
-// dtype, fan-in and flag of dlsim_pairwise_sqdist / _tensors
-int check_pairdist_scalars(int n, int dtype, int accumulate) {
-  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
-  if (n < 1) return fail(DLSIM_E_ARG, "n must be >= 1 (got %d)", n);
-  if (n > DLSIM_MAX_PAIRDIST_INPUTS)
-    return fail(DLSIM_E_ARG, "n must be <= %d (got %d): the pairs' accumulators are held in registers",
-                DLSIM_MAX_PAIRDIST_INPUTS, n);
-  if (accumulate != 0 && accumulate != 1) return fail(DLSIM_E_ARG, "accumulate must be 0 or 1 (got %d)", accumulate);
-  return DLSIM_OK;
-}
-
-// The n inputs of one tensor (stride apart in `in`) against the matrix: no
-// null pointer, no byte shared with d2. The inputs may alias each other.
-// Zero-byte inputs are never read: any pointer will do (torch gives null).
-int check_pairdist_buffers(const void* const* in, size_t stride, int n, size_t bytes, const double* d2) {
-  if (bytes == 0) return DLSIM_OK;
-  const uintptr_t o0 = reinterpret_cast<uintptr_t>(d2), o1 = o0 + sizeof(double) * static_cast<size_t>(n) * n;
-  for (int i = 0; i < n; ++i) {
-    const void* p = in[static_cast<size_t>(i) * stride];
-    if (!p) return fail(DLSIM_E_ARG, "null input pointer at index %d", i);
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
-    if (a0 < o1 && o0 < a0 + bytes) return fail(DLSIM_E_ARG, "the distance matrix overlaps input %d", i);
-  }
-  return DLSIM_OK;
-}
-
-// The fused reduce-and-measure dispatch (inst_reducedist.hip): arguments already checked.
-hipError_t reducedist_flat(const void* const* in, int n, const double* w, void* out, size_t nelem, int dtype,
-                           double* d2, int accumulate, hipStream_t st);
-void reducedist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
-
-// dtype, fan-in and flag of dlsim_wreduce_dist / _tensors
-int check_reducedist_scalars(int n, int dtype, int accumulate) {
-  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
-  if (n < 1) return fail(DLSIM_E_ARG, "n must be >= 1 (got %d)", n);
-  if (n > DLSIM_MAX_REDUCEDIST_INPUTS)
-    return fail(DLSIM_E_ARG, "n must be <= %d (got %d): the inputs' rows and accumulators are held in registers",
-                DLSIM_MAX_REDUCEDIST_INPUTS, n);
-  if (accumulate != 0 && accumulate != 1) return fail(DLSIM_E_ARG, "accumulate must be 0 or 1 (got %d)", accumulate);
-  return DLSIM_OK;
+  return check_outputs_apart(t, d_out, offs, n_elems, esz);
 }
 
 // The kernel uses the fp32 value of a weight unless the buffers are fp64: a
@@ -393,23 +361,10 @@ int check_reducedist_weights(const double* w, int n, int dtype) {
   return DLSIM_OK;
 }
 
-// The n inputs of one tensor (stride apart in `in`) of `bytes` bytes each
-// against one output range (out null or out_bytes 0: none) and the distance vector:
-// no null input, no byte shared. The inputs may alias each other.
-int check_reducedist_buffers(const void* const* in, size_t stride, int n, size_t bytes, const void* out,
-                             size_t out_bytes, const double* d2) {
-  if (bytes == 0) return DLSIM_OK;
-  if (out_bytes == 0) out = nullptr;
-  const uintptr_t v0 = reinterpret_cast<uintptr_t>(d2), v1 = v0 + sizeof(double) * static_cast<size_t>(n);
-  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + out_bytes;
-  if (out && o0 < v1 && v0 < o1) return fail(DLSIM_E_ARG, "the distance vector overlaps the output");
-  for (int i = 0; i < n; ++i) {
-    const void* p = in[static_cast<size_t>(i) * stride];
-    if (!p) return fail(DLSIM_E_ARG, "null input pointer at index %d", i);
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
-    if (a0 < v1 && v0 < a0 + bytes) return fail(DLSIM_E_ARG, "the distance vector overlaps input %d", i);
-    if (out && a0 < o1 && o0 < a0 + bytes) return fail(DLSIM_E_ARG, "output overlaps input %d", i);
-  }
+// The n doubles at d2 against one non-empty output range of dlsim_wreduce_dist
+int check_vector_off_output(const double* d2, int n, uintptr_t o0, size_t out_bytes) {
+  if (out_bytes && o0 < addr(d2) + sizeof(double) * static_cast<size_t>(n) && addr(d2) < o0 + out_bytes)
+    return fail(DLSIM_E_ARG, "the distance vector overlaps the output");
   return DLSIM_OK;
 }
 
@@ -1207,11 +1162,15 @@ int dlsim_sgd_momentum_step_tensors(int t, const void* const* d_params, const vo
 int dlsim_robust_reduce(const void* const* d_inputs, int n, int lo, int hi, void* d_out, size_t n_elems, int dtype,
                         void* stream) {
   g_err.clear();
-  int rc = check_robust_window(n, lo, hi, dtype);
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_INPUTS, dtype, kRobustLimit);
+  if (rc == DLSIM_OK) rc = check_robust_window(n, lo, hi);
   if (rc != DLSIM_OK) return rc;
   if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
   if (n_elems == 0) return DLSIM_OK;
-  rc = check_robust_buffers(d_inputs, 1, n, d_out, n_elems * elem_bytes(dtype));
+  if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+  // any shared byte is rejected (exact aliasing too: unlike the weighted reduce this is not declared in place)
+  const size_t bytes = n_elems * elem_bytes(dtype);
+  rc = check_inputs_apart(d_inputs, 1, n, bytes, addr(d_out), addr(d_out) + bytes, "output");
   if (rc != DLSIM_OK) return rc;
   const hipError_t e = robust_flat(d_inputs, n, lo, hi, d_out, n_elems, dtype, static_cast<hipStream_t>(stream));
   return e == hipSuccess ? DLSIM_OK : hip_fail(e, "robust reduce launch");
@@ -1221,38 +1180,17 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
                                 const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype, void* stream) {
   g_err.clear();
   if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
-  int rc = check_robust_window(n, lo, hi, dtype);
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_INPUTS, dtype, kRobustLimit);
+  if (rc == DLSIM_OK) rc = check_robust_window(n, lo, hi);
   if (rc != DLSIM_OK || t == 0) return rc;
   if (!d_inputs || !n_elems || !out_off_bytes) return fail(DLSIM_E_ARG, "null array argument");
-  const size_t esz = elem_bytes(dtype);
-  const size_t ts = static_cast<size_t>(t);
-  // Every tensor's output range against every input of every tensor (the
-  // tensors run as launches in order on one stream) and against the other
-  // outputs; all before the first launch.
-  for (int k = 0; k < t; ++k) {
-    if (n_elems[k] == 0) continue;
-    if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out) + out_off_bytes[k], o1 = o0 + n_elems[k] * esz;
-    for (int j = 0; j < t; ++j) {
-      if (n_elems[j] == 0) continue;
-      const size_t bytes = n_elems[j] * esz;
-      for (int i = 0; i < n; ++i) {
-        const void* p = d_inputs[static_cast<size_t>(i) * ts + j];
-        if (!p) return fail(DLSIM_E_ARG, "null input pointer (model %d, tensor %d)", i, j);
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
-        if (a0 < o1 && o0 < a0 + bytes)
-          return fail(DLSIM_E_ARG, "output of tensor %d overlaps tensor %d of model %d", k, j, i);
-      }
-      const uintptr_t q0 = reinterpret_cast<uintptr_t>(d_out) + out_off_bytes[j];
-      if (j != k && q0 < o1 && o0 < q0 + bytes)
-        return fail(DLSIM_E_ARG, "outputs of tensors %d and %d overlap", k, j);
-    }
-  }
+  rc = check_tensor_outputs(d_inputs, n, t, n_elems, d_out, out_off_bytes, elem_bytes(dtype));
+  if (rc != DLSIM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const void* row[DLSIM_MAX_ROBUST_INPUTS];
   for (int k = 0; k < t; ++k) {
     if (n_elems[k] == 0) continue;
-    for (int i = 0; i < n; ++i) row[i] = d_inputs[static_cast<size_t>(i) * ts + k];
+    gather_row(d_inputs, n, t, k, row);
     const hipError_t e =
         robust_flat(row, n, lo, hi, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
     if (e != hipSuccess) return hip_fail(e, "robust reduce launch");
@@ -1263,11 +1201,13 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
 int dlsim_pairwise_sqdist(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,
                           void* stream) {
   g_err.clear();
-  int rc = check_pairdist_scalars(n, dtype, accumulate);
+  int rc = check_fan_in(n, DLSIM_MAX_PAIRDIST_INPUTS, dtype, kPairdistLimit);
+  if (rc == DLSIM_OK) rc = check_accumulate(accumulate);
   if (rc != DLSIM_OK) return rc;
   if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
   if (!d_d2) return fail(DLSIM_E_ARG, "null distance matrix pointer");
-  rc = check_pairdist_buffers(d_inputs, 1, n, n_elems * elem_bytes(dtype), d_d2);
+  rc = check_inputs_apart(d_inputs, 1, n, n_elems * elem_bytes(dtype), addr(d_d2),
+                          addr(d_d2) + sizeof(double) * static_cast<size_t>(n) * n, "the distance matrix");
   if (rc != DLSIM_OK) return rc;
   const hipError_t e = pairdist_flat(d_inputs, n, n_elems, dtype, d_d2, accumulate, static_cast<hipStream_t>(stream));
   return e == hipSuccess ? DLSIM_OK : hip_fail(e, "pairwise distance launch");
@@ -1277,13 +1217,15 @@ int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, con
                                   double* d_d2, int accumulate, void* stream) {
   g_err.clear();
   if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
-  int rc = check_pairdist_scalars(n, dtype, accumulate);
+  int rc = check_fan_in(n, DLSIM_MAX_PAIRDIST_INPUTS, dtype, kPairdistLimit);
+  if (rc == DLSIM_OK) rc = check_accumulate(accumulate);
   if (rc != DLSIM_OK) return rc;
   if (!d_d2) return fail(DLSIM_E_ARG, "null distance matrix pointer");
   if (t > 0 && (!d_inputs || !n_elems)) return fail(DLSIM_E_ARG, "null array argument");
   const size_t ts = static_cast<size_t>(t);
   for (int k = 0; k < t; ++k) {
-    rc = check_pairdist_buffers(d_inputs + k, ts, n, n_elems[k] * elem_bytes(dtype), d_d2);
+    rc = check_inputs_apart(d_inputs + k, ts, n, n_elems[k] * elem_bytes(dtype), addr(d_d2),
+                            addr(d_d2) + sizeof(double) * static_cast<size_t>(n) * n, "the distance matrix");
     if (rc != DLSIM_OK) return fail(rc, "tensor %d: %s", k, std::string(g_err).c_str());
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1293,7 +1235,7 @@ int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, con
   }
   const void* row[DLSIM_MAX_PAIRDIST_INPUTS];
   for (int k = 0; k < t; ++k) {
-    for (int i = 0; i < n; ++i) row[i] = d_inputs[static_cast<size_t>(i) * ts + k];
+    gather_row(d_inputs, n, t, k, row);
     const hipError_t e = pairdist_flat(row, n, n_elems[k], dtype, d_d2, k == 0 ? accumulate : 1, st);
     if (e != hipSuccess) return hip_fail(e, "pairwise distance launch");
   }
@@ -1302,7 +1244,7 @@ int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, con
 
 int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks) {
   g_err.clear();
-  const int rc = check_pairdist_scalars(n, dtype, 0);
+  const int rc = check_fan_in(n, DLSIM_MAX_PAIRDIST_INPUTS, dtype, kPairdistLimit);
   if (rc != DLSIM_OK) return rc;
   if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
   pairdist_geometry(n, dtype, n_elems, tile_elems, blocks);
@@ -1312,13 +1254,19 @@ int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems
 int dlsim_wreduce_dist(const void* const* d_inputs, int n, const double* h_weights, void* d_out, size_t n_elems,
                        int dtype, double* d_d2, int accumulate, void* stream) {
   g_err.clear();
-  int rc = check_reducedist_scalars(n, dtype, accumulate);
+  int rc = check_fan_in(n, DLSIM_MAX_REDUCEDIST_INPUTS, dtype, kReducedistLimit);
+  if (rc == DLSIM_OK) rc = check_accumulate(accumulate);
   if (rc != DLSIM_OK) return rc;
   if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
   if (!d_d2) return fail(DLSIM_E_ARG, "null distance vector pointer");
   rc = check_reducedist_weights(h_weights, n, dtype);
   if (rc != DLSIM_OK) return rc;
-  rc = check_reducedist_buffers(d_inputs, 1, n, n_elems * elem_bytes(dtype), d_out, n_elems * elem_bytes(dtype), d_d2);
+  const size_t bytes = n_elems * elem_bytes(dtype);
+  if (d_out) rc = check_vector_off_output(d_d2, n, addr(d_out), bytes);
+  if (rc == DLSIM_OK)
+    rc = check_inputs_apart(d_inputs, 1, n, bytes, addr(d_d2), addr(d_d2) + sizeof(double) * static_cast<size_t>(n),
+                            "the distance vector");
+  if (rc == DLSIM_OK && d_out) rc = check_inputs_apart(d_inputs, 1, n, bytes, addr(d_out), addr(d_out) + bytes, "output");
   if (rc != DLSIM_OK) return rc;
   const hipError_t e = reducedist_flat(d_inputs, n, h_weights, d_out, n_elems, dtype, d_d2, accumulate,
                                        static_cast<hipStream_t>(stream));
@@ -1330,28 +1278,25 @@ int dlsim_wreduce_dist_tensors(const void* const* d_inputs, int n, int t, const 
                                double* d_d2, int accumulate, void* stream) {
   g_err.clear();
   if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
-  int rc = check_reducedist_scalars(n, dtype, accumulate);
+  int rc = check_fan_in(n, DLSIM_MAX_REDUCEDIST_INPUTS, dtype, kReducedistLimit);
+  if (rc == DLSIM_OK) rc = check_accumulate(accumulate);
   if (rc != DLSIM_OK) return rc;
   if (!d_d2) return fail(DLSIM_E_ARG, "null distance vector pointer");
   rc = check_reducedist_weights(h_weights, n, dtype);
   if (rc != DLSIM_OK) return rc;
   if (t > 0 && (!d_inputs || !n_elems || (d_out && !out_off_bytes))) return fail(DLSIM_E_ARG, "null array argument");
   const size_t esz = elem_bytes(dtype);
-  const size_t ts = static_cast<size_t>(t);
-  // Every tensor's output range against every input of every tensor (the
-  // tensors run as launches in order on one stream), the distance vector and
-  // the other outputs; all before the first launch.
+  // The distance vector against every output range and every input, then the
+  // output ranges as dlsim_robust_reduce_tensors; all before the first launch.
   for (int k = 0; k < t; ++k) {
-    const char* const ok = d_out ? static_cast<const char*>(d_out) + out_off_bytes[k] : nullptr;
-    for (int j = 0; j < t; ++j) {
-      rc = check_reducedist_buffers(d_inputs + j, ts, n, n_elems[j] * esz, ok, n_elems[k] * esz, d_d2);
-      if (rc != DLSIM_OK) return fail(rc, "output of tensor %d, inputs of tensor %d: %s", k, j, std::string(g_err).c_str());
-      if (!ok || j == k || n_elems[k] == 0 || n_elems[j] == 0) continue;
-      const uintptr_t o0 = reinterpret_cast<uintptr_t>(ok), o1 = o0 + n_elems[k] * esz;
-      const uintptr_t q0 = reinterpret_cast<uintptr_t>(d_out) + out_off_bytes[j];
-      if (q0 < o1 && o0 < q0 + n_elems[j] * esz) return fail(DLSIM_E_ARG, "outputs of tensors %d and %d overlap", k, j);
-    }
+    if (d_out) rc = check_vector_off_output(d_d2, n, addr(d_out) + out_off_bytes[k], n_elems[k] * esz);
+    if (rc == DLSIM_OK)
+      rc = check_inputs_apart(d_inputs + k, static_cast<size_t>(t), n, n_elems[k] * esz, addr(d_d2),
+                              addr(d_d2) + sizeof(double) * static_cast<size_t>(n), "the distance vector");
+    if (rc != DLSIM_OK) return fail(rc, "tensor %d: %s", k, std::string(g_err).c_str());
   }
+  if (d_out) rc = check_tensor_outputs(d_inputs, n, t, n_elems, d_out, out_off_bytes, esz);
+  if (rc != DLSIM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (t == 0) {
     const hipError_t e = reducedist_flat(nullptr, n, h_weights, nullptr, 0, dtype, d_d2, accumulate, st);
@@ -1359,7 +1304,7 @@ int dlsim_wreduce_dist_tensors(const void* const* d_inputs, int n, int t, const 
   }
   const void* row[DLSIM_MAX_REDUCEDIST_INPUTS];
   for (int k = 0; k < t; ++k) {
-    for (int i = 0; i < n; ++i) row[i] = d_inputs[static_cast<size_t>(i) * ts + k];
+    gather_row(d_inputs, n, t, k, row);
     void* const ok = d_out ? static_cast<char*>(d_out) + out_off_bytes[k] : nullptr;
     const hipError_t e = reducedist_flat(row, n, h_weights, ok, n_elems[k], dtype, d_d2, k == 0 ? accumulate : 1, st);
     if (e != hipSuccess) return hip_fail(e, "reduce-and-measure launch");
@@ -1369,7 +1314,7 @@ int dlsim_wreduce_dist_tensors(const void* const* d_inputs, int n, int t, const 
 
 int dlsim_reducedist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks) {
   g_err.clear();
-  const int rc = check_reducedist_scalars(n, dtype, 0);
+  const int rc = check_fan_in(n, DLSIM_MAX_REDUCEDIST_INPUTS, dtype, kReducedistLimit);
   if (rc != DLSIM_OK) return rc;
   if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
   reducedist_geometry(n, dtype, n_elems, tile_elems, blocks);

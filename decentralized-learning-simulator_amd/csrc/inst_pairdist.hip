@@ -4,16 +4,11 @@
 // dlsim_pairdist_geometry (dlsim_abi.hip checks the arguments).
 #include "pairdist_kernels.hpp"
 
-#include "dispatch.hpp"
+#include "partials.hpp"
 
 namespace dlsim_host __attribute__((visibility("hidden"))) {
 
 namespace {
-
-// Blocks of one launch, over all its units: four resident blocks (one wave
-// per SIMD each) on each of the 256 CUs of an MI355X. A constant, so that the
-// summation order is the same on every device.
-constexpr unsigned kPdGridBlocks = 1024;
 
 struct PdGeom {
   int cap;          // rows of a diagonal unit: 4 or 8
@@ -43,7 +38,7 @@ PdGeom pd_geometry(int n, int elems16, size_t nelem, bool vec) {
   }
   g.tile = static_cast<size_t>(dlsim::kBlock) * (vec ? elems16 : 1);
   const size_t tiles = (nelem + g.tile - 1) / g.tile;
-  const size_t cap = kPdGridBlocks / g.active;
+  const size_t cap = kDistGridBlocks / g.active;
   g.blocks = static_cast<unsigned>(std::min(cap, std::max<size_t>(tiles, 1)));
   return g;
 }
@@ -63,33 +58,21 @@ hipError_t pd_run(const void* const* in, int n, size_t nelem, double* d2, int ac
   for (int i = 0; i < n; ++i) vec = vec && aligned16(in[i]);
   dlsim::PdSlots s;
   std::memset(&s, 0, sizeof(s));
-  const int pairs = n * (n - 1) / 2;
-  const unsigned fin_blocks = static_cast<unsigned>((pairs + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
-  // Inputs too long for 32-bit byte offsets go as consecutive ranges (the
-  // launch limit of the library's other load paths); every range after the
-  // first accumulates.
-  const size_t range = kMaxLaunchOutBytes / Op::kBytes;
-  for (size_t o = 0; o < nelem; o += range) {
-    const size_t len = std::min(range, nelem - o);
+  // Inputs too long for 32-bit byte offsets go as consecutive ranges; every
+  // range after the first accumulates.
+  return for_each_range(nelem, Op::kBytes, [&](size_t o, size_t len) {
     for (int i = 0; i < n; ++i) s.p[i] = static_cast<const char*>(in[i]) + o * Op::kBytes;
     const PdGeom g = pd_geometry(n, Op::E, len, vec);
-    // the blocks' partials: stream-ordered, as the fan-in table of the reduce
-    void* ws = nullptr;
-    hipError_t e = hipMallocAsync(&ws, sizeof(double) * dlsim::kPdSlots * g.units * g.blocks, st);
-    if (e != hipSuccess) return e;
-    if (vec) pd_launch_main<Op, true>(g, s, n, len, static_cast<double*>(ws), st);
-    else pd_launch_main<Op, false>(g, s, n, len, static_cast<double*>(ws), st);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(dlsim::k_pairdist_finish<>, dim3(fin_blocks), dim3(dlsim::kBlock), 0, st,
+    return with_partials(static_cast<size_t>(dlsim::kPdSlots) * g.units * g.blocks, st, [&](double* ws) {
+      if (vec) pd_launch_main<Op, true>(g, s, n, len, ws, st);
+      else pd_launch_main<Op, false>(g, s, n, len, ws, st);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(dlsim::k_pairdist_finish<>, dim3(finish_blocks(n * (n - 1) / 2)), dim3(dlsim::kBlock), 0, st,
                          static_cast<const double*>(ws), g.blocks, n, g.cap, d2, (accumulate || o > 0) ? 1 : 0);
-      e = hipGetLastError();
-    }
-    const hipError_t e2 = hipFreeAsync(ws, st);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+      return hipGetLastError();
+    });
+  });
 }
 
 int pd_elems16(int dtype) { return dtype == DLSIM_F64 ? 2 : dtype == DLSIM_F32 ? 4 : 8; }

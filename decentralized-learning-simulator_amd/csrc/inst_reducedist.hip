@@ -4,16 +4,11 @@
 // (dlsim_abi.hip checks the arguments).
 #include "reducedist_kernels.hpp"
 
-#include "dispatch.hpp"
+#include "partials.hpp"
 
 namespace dlsim_host __attribute__((visibility("hidden"))) {
 
 namespace {
-
-// Blocks of one launch: four resident blocks (one wave per SIMD each) on each
-// of the 256 CUs of an MI355X, as the pairwise-distance kernels. A constant,
-// so that the summation order is the same on every device.
-constexpr unsigned kRdGridBlocks = 1024;
 
 struct RdGeom {
   int cap;          // compile-time row capacity: 4, 8, 16 or 32
@@ -25,17 +20,15 @@ struct RdGeom {
 RdGeom rd_geometry(int n, int elem_bytes, size_t nelem, bool vec) {
   RdGeom g;
   g.cap = n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
-  const int width = std::max(elem_bytes, g.cap <= 8 ? 16 : g.cap <= 16 ? 8 : 4);  // dlsim::rd_width
-  g.tile = static_cast<size_t>(dlsim::kBlock) * (vec ? width / elem_bytes : 1);
+  g.tile = static_cast<size_t>(dlsim::kBlock) * (vec ? dlsim::rd_width_bytes(elem_bytes, g.cap) / elem_bytes : 1);
   const size_t tiles = (nelem + g.tile - 1) / g.tile;
-  g.blocks = static_cast<unsigned>(std::min<size_t>(kRdGridBlocks, std::max<size_t>(tiles, 1)));
+  g.blocks = static_cast<unsigned>(std::min<size_t>(kDistGridBlocks, std::max<size_t>(tiles, 1)));
   return g;
 }
 
 template <class Op, bool VEC, class S>
 void rd_launch_main(const RdGeom& g, const S& s, int n, void* out, size_t nelem, double* ws, hipStream_t st) {
   const dim3 grid(g.blocks), block(dlsim::kBlock);
-  static_assert(dlsim::rd_width<Op, 32>() * 32 <= 256 && dlsim::rd_width<Op, 8>() == 16, "the register plan");
   if (g.cap == 4) hipLaunchKernelGGL((dlsim::k_reducedist<Op, 4, VEC>), grid, block, 0, st, s, n, out, nelem, ws);
   else if (g.cap == 8) hipLaunchKernelGGL((dlsim::k_reducedist<Op, 8, VEC>), grid, block, 0, st, s, n, out, nelem, ws);
   else if (g.cap == 16) hipLaunchKernelGGL((dlsim::k_reducedist<Op, 16, VEC>), grid, block, 0, st, s, n, out, nelem, ws);
@@ -53,33 +46,22 @@ hipError_t rd_run(const void* const* in, int n, const double* w, void* out, size
   dlsim::RdSlots<W> s;
   std::memset(&s, 0, sizeof(s));
   for (int i = 0; i < n; ++i) s.w[i] = static_cast<W>(w[i]);
-  const unsigned fin_blocks = static_cast<unsigned>((n + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
-  // Ranges too long for one launch's 32-bit byte offsets (the launch limit of
-  // the library's other paths; a multiple of every tile) go as consecutive
+  // Ranges too long for one launch's 32-bit byte offsets go as consecutive
   // pieces; every piece after the first accumulates.
-  const size_t range = kMaxLaunchOutBytes / F::kBytes;
-  for (size_t o = 0; o < nelem; o += range) {
-    const size_t len = std::min(range, nelem - o);
+  return for_each_range(nelem, F::kBytes, [&](size_t o, size_t len) {
     for (int i = 0; i < n; ++i) s.p[i] = static_cast<const char*>(in[i]) + o * F::kBytes;
     void* const outp = out ? static_cast<char*>(out) + o * F::kBytes : nullptr;
     const RdGeom g = rd_geometry(n, F::kBytes, len, vec);
-    // the blocks' partials: stream-ordered, as the pairwise-distance kernels'
-    void* ws = nullptr;
-    hipError_t e = hipMallocAsync(&ws, sizeof(double) * static_cast<size_t>(g.cap) * g.blocks, st);
-    if (e != hipSuccess) return e;
-    if (vec) rd_launch_main<Op, true>(g, s, n, outp, len, static_cast<double*>(ws), st);
-    else rd_launch_main<Op, false>(g, s, n, outp, len, static_cast<double*>(ws), st);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(dlsim::k_reducedist_finish, dim3(fin_blocks), dim3(dlsim::kBlock), 0, st,
+    return with_partials(static_cast<size_t>(g.cap) * g.blocks, st, [&](double* ws) {
+      if (vec) rd_launch_main<Op, true>(g, s, n, outp, len, ws, st);
+      else rd_launch_main<Op, false>(g, s, n, outp, len, ws, st);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(dlsim::k_reducedist_finish, dim3(finish_blocks(n)), dim3(dlsim::kBlock), 0, st,
                          static_cast<const double*>(ws), g.blocks, n, d2, (accumulate || o > 0) ? 1 : 0);
-      e = hipGetLastError();
-    }
-    const hipError_t e2 = hipFreeAsync(ws, st);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace

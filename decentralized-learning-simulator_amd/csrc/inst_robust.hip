@@ -3,7 +3,7 @@
 // dlsim_robust_reduce_tensors (dlsim_abi.hip checks the arguments).
 #include "robust_kernels.hpp"
 
-#include "dispatch.hpp"
+#include "partials.hpp"
 
 namespace dlsim_host __attribute__((visibility("hidden"))) {
 
@@ -37,9 +37,7 @@ hipError_t rob_launch_cap(const void* const* in, int n, int lo, int hi, void* ou
   }
   // buffer stores take 32-bit byte offsets: longer outputs go as consecutive
   // ranges (elements are independent; a multiple of every tile size)
-  const size_t range = kMaxLaunchOutBytes / Op::kBytes;
-  for (size_t o = 0; o < nelem; o += range) {
-    const size_t len = std::min(range, nelem - o);
+  return for_each_range(nelem, Op::kBytes, [&](size_t o, size_t len) {
     for (int i = 0; i < n; ++i) s.p[i] = static_cast<const char*>(in[i]) + o * Op::kBytes;
     void* const dst = static_cast<char*>(out) + o * Op::kBytes;
     if constexpr (kHalves) {
@@ -55,10 +53,8 @@ hipError_t rob_launch_cap(const void* const* in, int n, int lo, int hi, void* ou
       hipLaunchKernelGGL((dlsim::k_robust_tiles<Op, CAP, kVptCap, kStp>), dim3(static_cast<unsigned>(blocks)),
                          dim3(dlsim::kBlock), 0, st, s, n, lo, hi, dst, nvec, len);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipGetLastError();
+  });
 }
 
 template <class Op>

@@ -1,0 +1,43 @@
+// partials.hpp — what the host dispatches of the n <= 32 input families share (inst_robust.hip,
+// inst_pairdist.hip, inst_reducedist.hip): the split of a long input into launches of 32-bit byte
+// offsets, and the two distance families' grid cap, partial-sum workspace and finish grid. Host code only.
+#pragma once
+
+#include "dispatch.hpp"
+
+namespace dlsim_host __attribute__((visibility("hidden"))) {
+
+// Blocks of one distance launch, over all its units: four resident blocks (one wave per SIMD each) on
+// each of the 256 CUs of an MI355X. A constant, so that the summation order is the same on every device.
+constexpr unsigned kDistGridBlocks = 1024;
+
+// f(first element, elements) -> hipError_t for consecutive ranges of at most kMaxLaunchOutBytes (the
+// launch limit of the library's other paths; a multiple of every tile size). Stops at the first error.
+template <class F>
+hipError_t for_each_range(size_t nelem, size_t elem_bytes, F f) {
+  const size_t range = kMaxLaunchOutBytes / elem_bytes;
+  for (size_t o = 0; o < nelem; o += range) {
+    const hipError_t e = f(o, std::min(range, nelem - o));
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// body(ws) -> hipError_t with `doubles` doubles of device memory allocated and freed in stream order
+// (as the fan-in table of the reduce): the main launch writes the blocks' partials there, the finish
+// launch sums them. The body's error comes before the free's.
+template <class Body>
+hipError_t with_partials(size_t doubles, hipStream_t st, Body body) {
+  void* ws = nullptr;
+  hipError_t e = hipMallocAsync(&ws, sizeof(double) * doubles, st);
+  if (e != hipSuccess) return e;
+  e = body(static_cast<double*>(ws));
+  const hipError_t e2 = hipFreeAsync(ws, st);
+  return e == hipSuccess ? e2 : e;
+}
+
+inline unsigned finish_blocks(int items) {  // grid of a finish kernel: one wave per item (a pair, an input)
+  return static_cast<unsigned>((items + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
+}
+
+}  // namespace dlsim_host

@@ -74,10 +74,13 @@ struct RdSlots {
 };
 
 // bytes a lane takes of one row per tile on the vector path
+constexpr int rd_width_bytes(int elem_bytes, int cap) {
+  const int w = cap <= 8 ? 16 : cap <= 16 ? 8 : 4;
+  return w < elem_bytes ? elem_bytes : w;
+}
 template <class Op, int CAP>
 constexpr int rd_width() {
-  constexpr int w = CAP <= 8 ? 16 : CAP <= 16 ? 8 : 4;
-  return w < Op::Fold::kBytes ? Op::Fold::kBytes : w;
+  return rd_width_bytes(Op::Fold::kBytes, CAP);
 }
 
 // WB bytes at item idx, in the low dwords of a 16-byte vector (the rest zero,

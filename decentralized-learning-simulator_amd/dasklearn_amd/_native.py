@@ -481,14 +481,67 @@ def sgd_momentum_step_tensors_raw(param_ptrs: Sequence[int], grad_ptrs: Sequence
 SGD_MOMENTUM_TENSORS_PER_LAUNCH = 64  # csrc/sgdm_kernels.hpp kSgdmMaxTensors
 
 
+# ---- the entries over n <= 32 inputs: order statistics, pairwise distances, reduce-and-measure ----
 MAX_ROBUST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_ROBUST_INPUTS
+MAX_PAIRDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_PAIRDIST_INPUTS
+MAX_REDUCEDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_REDUCEDIST_INPUTS
+
+
+def _check_fan_in(n: int, limit: int, message: str) -> None:
+    """ValueError(message with its {limit} and {n} filled in) past the limit."""
+    if n > limit:
+        raise ValueError(message.format(limit=limit, n=n))
 
 
 def check_robust_fan_in(n: int) -> None:
-    """The order-statistic kernels sort their n inputs in registers."""
-    if n > MAX_ROBUST_INPUTS:
-        raise ValueError(f"the median and trimmed-mean kernels take at most {MAX_ROBUST_INPUTS} models "
-                         f"(got {n}): the sorting network is held in registers")
+    _check_fan_in(n, MAX_ROBUST_INPUTS, "the median and trimmed-mean kernels take at most {limit} models (got {n}): "
+                                        "the sorting network is held in registers")
+
+
+def check_pairdist_fan_in(n: int) -> None:
+    _check_fan_in(n, MAX_PAIRDIST_INPUTS, "the pairwise-distance kernels take at most {limit} models (got {n})")
+
+
+def check_reducedist_fan_in(n: int) -> None:
+    _check_fan_in(n, MAX_REDUCEDIST_INPUTS, "the reduce-and-measure kernels take at most {limit} models (got {n})")
+
+
+def _check_flat_inputs(inputs, out, device, what: str):
+    """(dtype, numel) of the n >= 1 contiguous device tensors of one dtype and
+    size on `device`, `out` (unless None) being one more of them."""
+    dt, numel = inputs[0].dtype, inputs[0].numel()
+    for t in list(inputs) + ([] if out is None else [out]):
+        if not t.is_cuda or t.device != device:
+            raise ValueError(f"the {what} needs device tensors on one device (no CPU path)")
+        if t.dtype != dt or t.numel() != numel or not t.is_contiguous():
+            raise ValueError("inputs and output must be contiguous, same dtype and size")
+    return dt, numel
+
+
+def _check_distances(d2, count: int, what: str) -> None:
+    import torch
+    if not d2.is_cuda or d2.dtype != torch.float64 or d2.numel() != count or not d2.is_contiguous():
+        raise ValueError(f"the distance {what} must be a contiguous float64 device tensor of {count} elements")
+
+
+def _ptr_array(ptrs):
+    """A ctypes array of the pointers (None: null), never of length 0."""
+    return (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+
+
+def _size_array(sizes):
+    return (ctypes.c_size_t * max(len(sizes), 1))(*sizes)
+
+
+def _double_array(values):
+    return (ctypes.c_double * len(values))(*[float(v) for v in values])
+
+
+def _geometry(symbol: str, n: int, torch_dtype, numel: int):
+    tile, blocks = ctypes.c_size_t(0), ctypes.c_uint(0)
+    _check(symbol, getattr(load(), symbol)(n, dtype_code(torch_dtype, single_task=True), numel, ctypes.byref(tile),
+                                           ctypes.byref(blocks)))
+    return tile.value, blocks.value
 
 
 def robust_reduce(inputs, lo: int, hi: int, out, stream=None):
@@ -500,16 +553,10 @@ def robust_reduce(inputs, lo: int, hi: int, out, stream=None):
     if n < 1:
         raise IndexError("list index out of range")
     check_robust_fan_in(n)
-    numel = out.numel()
-    for t in list(inputs) + [out]:
-        if not t.is_cuda or t.device != out.device:
-            raise ValueError("the robust reduce needs device tensors on one device (no CPU path)")
-        if t.dtype != out.dtype or t.numel() != numel or not t.is_contiguous():
-            raise ValueError("inputs and output must be contiguous, same dtype and size")
+    dt, numel = _check_flat_inputs(inputs, out, out.device, "robust reduce")
     _check("dlsim_robust_reduce",
-           load().dlsim_robust_reduce((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, int(lo), int(hi),
-                                      out.data_ptr(), numel, dtype_code(out.dtype, single_task=True),
-                                      _stream_handle(out.device, stream)))
+           load().dlsim_robust_reduce(_ptr_array([t.data_ptr() for t in inputs]), n, int(lo), int(hi), out.data_ptr(),
+                                      numel, dtype_code(dt, single_task=True), _stream_handle(out.device, stream)))
     return out
 
 
@@ -519,22 +566,11 @@ def robust_reduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[i
     (the arena path: every tensor checked against models[0]'s layout, on the
     output's device, contiguous). in_ptrs model-major (tensor k of model i at
     i * t + k); output tensor k at out_base + out_offsets[k] bytes."""
-    t = len(numels)
     check_robust_fan_in(n)
     _check("dlsim_robust_reduce_tensors",
-           load().dlsim_robust_reduce_tensors((ctypes.c_void_p * max(len(in_ptrs), 1))(*in_ptrs), n, t,
-                                              (ctypes.c_size_t * max(t, 1))(*numels),
-                                              (ctypes.c_size_t * max(t, 1))(*out_offsets), int(lo), int(hi),
-                                              out_base, dtype, stream_handle))
-
-
-MAX_PAIRDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_PAIRDIST_INPUTS
-
-
-def check_pairdist_fan_in(n: int) -> None:
-    """The distance kernels hold one accumulator per pair of a row group in registers."""
-    if n > MAX_PAIRDIST_INPUTS:
-        raise ValueError(f"the pairwise-distance kernels take at most {MAX_PAIRDIST_INPUTS} models (got {n})")
+           load().dlsim_robust_reduce_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
+                                              _size_array(out_offsets), int(lo), int(hi), out_base, dtype,
+                                              stream_handle))
 
 
 def pairwise_sqdist(inputs, out, accumulate: bool = False, stream=None):
@@ -544,21 +580,14 @@ def pairwise_sqdist(inputs, out, accumulate: bool = False, stream=None):
     memory with an input (the inputs may alias each other). accumulate: add to
     what `out` holds (bitwise symmetric, diagonal +0.0, as a call without it
     leaves it). Deterministic (no atomics). Stream-ordered."""
-    import torch
     n = len(inputs)
     if n < 1:
         raise IndexError("list index out of range")
     check_pairdist_fan_in(n)
-    if not out.is_cuda or out.dtype != torch.float64 or out.numel() != n * n or not out.is_contiguous():
-        raise ValueError(f"the distance matrix must be a contiguous float64 device tensor of {n * n} elements")
-    dt, numel = inputs[0].dtype, inputs[0].numel()
-    for t in inputs:
-        if not t.is_cuda or t.device != out.device:
-            raise ValueError("the pairwise distance needs device tensors on one device (no CPU path)")
-        if t.dtype != dt or t.numel() != numel or not t.is_contiguous():
-            raise ValueError("inputs must be contiguous, same dtype and size")
+    _check_distances(out, n * n, "matrix")
+    dt, numel = _check_flat_inputs(inputs, None, out.device, "pairwise distance")
     _check("dlsim_pairwise_sqdist",
-           load().dlsim_pairwise_sqdist((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, numel,
+           load().dlsim_pairwise_sqdist(_ptr_array([t.data_ptr() for t in inputs]), n, numel,
                                         dtype_code(dt, single_task=True), out.data_ptr(), int(bool(accumulate)),
                                         _stream_handle(out.device, stream)))
     return out
@@ -566,34 +595,17 @@ def pairwise_sqdist(inputs, out, accumulate: bool = False, stream=None):
 
 def pairwise_sqdist_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], dtype: int, out_ptr: int,
                                 accumulate: bool, stream_handle) -> None:
-    """dlsim_pairwise_sqdist_tensors on pointers the caller has already
-    validated (the arena path). in_ptrs model-major (tensor k of model i at
-    i * t + k); the n*n doubles at out_ptr."""
-    t = len(numels)
+    """dlsim_pairwise_sqdist_tensors, as robust_reduce_tensors_raw; the n*n doubles at out_ptr."""
     check_pairdist_fan_in(n)
     _check("dlsim_pairwise_sqdist_tensors",
-           load().dlsim_pairwise_sqdist_tensors((ctypes.c_void_p * max(len(in_ptrs), 1))(*in_ptrs), n, t,
-                                                (ctypes.c_size_t * max(t, 1))(*numels), dtype, out_ptr,
-                                                int(bool(accumulate)), stream_handle))
+           load().dlsim_pairwise_sqdist_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels), dtype,
+                                                out_ptr, int(bool(accumulate)), stream_handle))
 
 
 def pairdist_geometry(n: int, torch_dtype, numel: int):
     """(tile elements, blocks) of dlsim_pairwise_sqdist for n 16-byte-aligned
     inputs of numel elements (dlsim_pairdist_geometry; no GPU needed)."""
-    tile, blocks = ctypes.c_size_t(0), ctypes.c_uint(0)
-    _check("dlsim_pairdist_geometry",
-           load().dlsim_pairdist_geometry(n, dtype_code(torch_dtype, single_task=True), numel, ctypes.byref(tile),
-                                          ctypes.byref(blocks)))
-    return tile.value, blocks.value
-
-
-MAX_REDUCEDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_REDUCEDIST_INPUTS
-
-
-def check_reducedist_fan_in(n: int) -> None:
-    """The fused kernels hold every input's row and accumulator in registers."""
-    if n > MAX_REDUCEDIST_INPUTS:
-        raise ValueError(f"the reduce-and-measure kernels take at most {MAX_REDUCEDIST_INPUTS} models (got {n})")
+    return _geometry("dlsim_pairdist_geometry", n, torch_dtype, numel)
 
 
 def wreduce_dist(inputs, weights: Sequence[float], out, d2, accumulate: bool = False, stream=None):
@@ -605,23 +617,15 @@ def wreduce_dist(inputs, weights: Sequence[float], out, d2, accumulate: bool = F
     contiguous float64 device tensor of n elements) share no memory with an
     input or each other. accumulate: add to what `d2` holds. Deterministic (no
     atomics). Stream-ordered."""
-    import torch
     n = len(inputs)
     if n < 1:
         raise IndexError("list index out of range")
     check_reducedist_fan_in(n)
     assert len(weights) == n
-    if not d2.is_cuda or d2.dtype != torch.float64 or d2.numel() != n or not d2.is_contiguous():
-        raise ValueError(f"the distance vector must be a contiguous float64 device tensor of {n} elements")
-    dt, numel = inputs[0].dtype, inputs[0].numel()
-    for t in list(inputs) + ([] if out is None else [out]):
-        if not t.is_cuda or t.device != d2.device:
-            raise ValueError("the reduce-and-measure needs device tensors on one device (no CPU path)")
-        if t.dtype != dt or t.numel() != numel or not t.is_contiguous():
-            raise ValueError("inputs and output must be contiguous, same dtype and size")
+    _check_distances(d2, n, "vector")
+    dt, numel = _check_flat_inputs(inputs, out, d2.device, "reduce-and-measure")
     _check("dlsim_wreduce_dist",
-           load().dlsim_wreduce_dist((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n,
-                                     (ctypes.c_double * n)(*[float(w) for w in weights]),
+           load().dlsim_wreduce_dist(_ptr_array([t.data_ptr() for t in inputs]), n, _double_array(weights),
                                      None if out is None else out.data_ptr(), numel,
                                      dtype_code(dt, single_task=True), d2.data_ptr(), int(bool(accumulate)),
                                      _stream_handle(d2.device, stream)))
@@ -631,27 +635,18 @@ def wreduce_dist(inputs, weights: Sequence[float], out, d2, accumulate: bool = F
 def wreduce_dist_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], out_offsets: Sequence[int],
                              weights: Sequence[float], out_base: Optional[int], dtype: int, d2_ptr: int,
                              accumulate: bool, stream_handle) -> None:
-    """dlsim_wreduce_dist_tensors on pointers the caller has already validated
-    (the arena path). in_ptrs model-major (tensor k of model i at i * t + k);
-    output tensor k at out_base + out_offsets[k] bytes; n doubles at d2_ptr."""
-    t = len(numels)
+    """dlsim_wreduce_dist_tensors, as robust_reduce_tensors_raw; the n doubles at d2_ptr."""
     check_reducedist_fan_in(n)
     _check("dlsim_wreduce_dist_tensors",
-           load().dlsim_wreduce_dist_tensors((ctypes.c_void_p * max(len(in_ptrs), 1))(*in_ptrs), n, t,
-                                             (ctypes.c_size_t * max(t, 1))(*numels),
-                                             (ctypes.c_size_t * max(t, 1))(*out_offsets),
-                                             (ctypes.c_double * n)(*[float(w) for w in weights]), out_base, dtype,
+           load().dlsim_wreduce_dist_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
+                                             _size_array(out_offsets), _double_array(weights), out_base, dtype,
                                              d2_ptr, int(bool(accumulate)), stream_handle))
 
 
 def reducedist_geometry(n: int, torch_dtype, numel: int):
     """(tile elements, blocks) of dlsim_wreduce_dist for n 16-byte-aligned
     inputs of numel elements (dlsim_reducedist_geometry; no GPU needed)."""
-    tile, blocks = ctypes.c_size_t(0), ctypes.c_uint(0)
-    _check("dlsim_reducedist_geometry",
-           load().dlsim_reducedist_geometry(n, dtype_code(torch_dtype, single_task=True), numel, ctypes.byref(tile),
-                                            ctypes.byref(blocks)))
-    return tile.value, blocks.value
+    return _geometry("dlsim_reducedist_geometry", n, torch_dtype, numel)
 
 
 DLSIM_ALLOC_CONTIGUOUS = 1

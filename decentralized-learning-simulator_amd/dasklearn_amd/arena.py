@@ -1432,329 +1432,6 @@ def _restride(out: nn.Module, layout: ParamLayout) -> nn.Module:
     return out
 
 
-def _robust_rows(all_params, idx, total: int, dt: torch.dtype, dev: torch.device):
-    """One device row per model holding its dtype group in layout order (host
-    models through one page-locked block and plain copies; models on another
-    device through .to). Returns (rows, page-locked block or None): the block
-    must outlive the copies queued on the current stream."""
-    n = len(all_params)
-    esz = _elem_size(dt)
-    stride = row_stride(total, esz)
-    flat = aligned_empty(n * stride, dt, dev, base_align(total * esz, esz))
-    rows = [flat[i * stride:i * stride + total] for i in range(n)]
-    pinned = None
-    for i, ps in enumerate(all_params):
-        parts = [ps[k].detach().reshape(-1) for k in idx]
-        if any(q.is_cuda for q in parts):
-            torch.cat([q.to(dev) for q in parts], out=rows[i])
-            continue
-        if pinned is None:
-            pinned = torch.empty(n * total, dtype=dt, pin_memory=True)
-        h = pinned[i * total:(i + 1) * total]
-        torch.cat(parts, out=h)
-        rows[i].copy_(h, non_blocking=True)
-    return rows, pinned
-
-
-def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Optional[bool] = None) -> nn.Module:
-    """The coordinate-wise order-statistic aggregate of `models` on the GPU
-    (dlsim_robust_reduce): per parameter element the n models' values are
-    sorted and the window [lo, hi) = lo_hi_fn(n) of them is averaged. As
-    aggregate_modules: a new module with copy.deepcopy(models[0]) semantics
-    (buffers and attributes are models[0]'s), the models only read, one launch
-    per dtype group, the result where models[0] lives unless to_host says
-    otherwise. A model whose parameter list differs from models[0]'s raises
-    ValueError (no zip semantics here); more than 32 models too.
-
-    Device-arena models are read in place, separate device tensors through
-    dlsim_robust_reduce_tensors, host models are copied into one device row
-    per model and dtype."""
-    model0 = models[0]  # IndexError for an empty list, as FedAvg
-    n = len(models)
-    _native.check_robust_fan_in(n)
-    lo, hi = lo_hi_fn(n)
-    layout, all_params, in_views = input_arenas(models)  # ZipMismatch is a ValueError
-    host_out = (not any(p.is_cuda for p in layout.params)) if to_host is None else to_host
-    dev = _target_device(all_params[0], device)
-    dix = dev.index
-    outs: Dict[torch.dtype, torch.Tensor] = {}
-    staged = False
-    keep = []  # page-locked blocks and contiguous copies the queued work reads
-    with torch.no_grad(), torch.cuda.device(dev):
-        raw_stream = torch._C._cuda_getCurrentRawStream(dix)
-        for dt, idx in layout.groups.items():
-            total = layout.totals[dt]
-            if total == 0:
-                outs[dt] = torch.empty(0, dtype=dt, device="cpu" if host_out else dev)
-                continue
-            out = outs[dt] = arena_empty(total, dt, dev)
-            views = in_views[dt]
-            if views is not None and all(v.get_device() == dix for v in views):
-                _native.robust_reduce(views, lo, hi, out)
-                continue
-            if all(ps[k].get_device() == dix for ps in all_params for k in idx):
-                copies, ptrs = _data_ptrs(all_params, idx)
-                keep.append(copies)
-                staged = staged or bool(copies)
-                _native.robust_reduce_tensors_raw(ptrs, n, layout.split_sizes[dt], layout.byte_offsets[dt], lo, hi,
-                                                  out.data_ptr(), _native.dtype_code(dt, single_task=True),
-                                                  raw_stream)
-                continue
-            rows, pinned = _robust_rows(all_params, idx, total, dt, dev)
-            keep.append(pinned)
-            staged = True
-            _native.robust_reduce(rows, lo, hi, out)
-        stream = torch.cuda.current_stream(dev)
-        if host_out:
-            left = {dt: a for dt, a in outs.items() if a.is_cuda}
-            outs.update(arenas_to_host(left, stream))  # waits for the stream
-        elif any(k is not None and len(k) for k in keep):
-            stream.synchronize()  # the staged copies' sources may go now
-    out = module_from_arenas(model0, layout, outs)
-    return _restride(out, layout) if staged else out
-
-
-def model_distances(models: List[nn.Module], device=None) -> torch.Tensor:
-    """The [n, n] float64 host matrix of squared L2 distances between the
-    models' parameters (dlsim_pairwise_sqdist): entry [i][j] is the sum over
-    every parameter element of (double(x_i) - double(x_j))^2, bitwise
-    symmetric, the diagonal +0.0. Parameters only, as the aggregators. The
-    dtype groups of models[0]'s layout add into the one matrix in layout
-    order. A model whose parameter list differs from models[0]'s raises
-    ValueError; more than 32 models too; an empty list IndexError.
-
-    The three input routes of robust_modules: device arenas are read in place,
-    separate device tensors go through dlsim_pairwise_sqdist_tensors, host
-    models are copied into one device row per model and dtype. The matrix
-    comes back with one D2H copy of n*n doubles, which waits for the stream."""
-    models[0]  # IndexError for an empty list, as the aggregators
-    n = len(models)
-    _native.check_pairdist_fan_in(n)
-    layout, all_params, in_views = input_arenas(models)  # ZipMismatch is a ValueError
-    dev = _target_device(all_params[0], device)
-    dix = dev.index
-    keep = []  # page-locked blocks and contiguous copies the queued work reads
-    with torch.no_grad(), torch.cuda.device(dev):
-        raw_stream = torch._C._cuda_getCurrentRawStream(dix)
-        d2 = torch.empty(n * n, dtype=torch.float64, device=dev)
-        first = True
-        for dt, idx in layout.groups.items():
-            total = layout.totals[dt]
-            if total == 0:
-                continue
-            views = in_views[dt]
-            if views is not None and all(v.get_device() == dix for v in views):
-                _native.pairwise_sqdist(views, d2, accumulate=not first)
-            elif all(ps[k].get_device() == dix for ps in all_params for k in idx):
-                copies, ptrs = _data_ptrs(all_params, idx)
-                keep.append(copies)
-                _native.pairwise_sqdist_tensors_raw(ptrs, n, layout.split_sizes[dt],
-                                                    _native.dtype_code(dt, single_task=True), d2.data_ptr(),
-                                                    not first, raw_stream)
-            else:
-                rows, pinned = _robust_rows(all_params, idx, total, dt, dev)
-                keep.append((rows, pinned))
-                _native.pairwise_sqdist(rows, d2, accumulate=not first)
-            first = False
-        if first:
-            d2.zero_()
-        host = d2.cpu()  # waits for the stream: the staged copies' sources may go now
-    del keep
-    return host.reshape(n, n)
-
-
-class ReduceDistPlan:
-    """The inputs of the fused reduce-and-measure kernel (dlsim_wreduce_dist)
-    for a list of models, resolved once and run any number of times: the
-    iterations of the geometric median and of centered clipping
-    (gradient_aggregation/geomed.py) read the same rows with new weights.
-
-    The three input routes of robust_modules / model_distances, per dtype
-    group: device arenas are read in place, separate device tensors go through
-    dlsim_wreduce_dist_tensors, host models are copied into one device row per
-    model and dtype (once, here). A model whose parameter list differs from
-    models[0]'s raises ValueError, more than 32 models too, an empty list
-    IndexError."""
-
-    def __init__(self, models: List[nn.Module], device=None):
-        self.model0 = models[0]  # IndexError for an empty list, as FedAvg
-        n = self.n = len(models)
-        _native.check_reducedist_fan_in(n)
-        layout, all_params, in_views = input_arenas(models)  # ZipMismatch is a ValueError
-        self.layout = layout
-        self.dev = dev = _target_device(all_params[0], device)
-        dix = dev.index
-        self.keep = []  # page-locked blocks and contiguous copies the queued work reads
-        self.staged = False
-        # per dtype: ("flat", one flat tensor per model) or ("tensors", one pointer list per model)
-        self.routes = {}
-        with torch.no_grad(), torch.cuda.device(dev):
-            for dt, idx in layout.groups.items():
-                total = layout.totals[dt]
-                if total == 0:
-                    continue
-                views = in_views[dt]
-                if views is not None and all(v.get_device() == dix for v in views):
-                    self.routes[dt] = ("flat", list(views))
-                elif all(ps[k].get_device() == dix for ps in all_params for k in idx):
-                    copies, ptrs = _data_ptrs(all_params, idx)
-                    self.keep.append(copies)
-                    self.staged = self.staged or bool(copies)
-                    t = len(idx)
-                    ptrs = list(ptrs)
-                    self.routes[dt] = ("tensors", [ptrs[i * t:(i + 1) * t] for i in range(n)])
-                else:
-                    rows, pinned = _robust_rows(all_params, idx, total, dt, dev)
-                    self.keep.append(pinned)
-                    self.staged = True
-                    self.routes[dt] = ("flat", rows)
-
-    def host_out(self, to_host: Optional[bool]) -> bool:
-        return (not any(p.is_cuda for p in self.layout.params)) if to_host is None else to_host
-
-    def run(self, idx: Sequence[int], weights: Sequence[float], center=None, want_out: bool = True):
-        """One pass over the models `idx` (behind `center`, a dict of flat
-        device arenas per dtype as an earlier pass returned it, as input 0 when
-        given) with one weight per input. Returns (dict dtype -> new device
-        arena, or {} without want_out; the float64 device vector of squared
-        distances, one per input). Dtype groups accumulate into the one vector
-        in layout order. Stream-ordered: nothing waits."""
-        layout, dev = self.layout, self.dev
-        idx = list(idx)
-        m = len(idx) + (center is not None)
-        assert len(weights) == m
-        outs: Dict[torch.dtype, torch.Tensor] = {}
-        with torch.no_grad(), torch.cuda.device(dev):
-            raw_stream = torch._C._cuda_getCurrentRawStream(dev.index)
-            d2 = torch.empty(m, dtype=torch.float64, device=dev)
-            first = True
-            for dt in layout.groups:
-                total = layout.totals[dt]
-                if total == 0:
-                    if want_out:
-                        outs[dt] = torch.empty(0, dtype=dt, device=dev)
-                    continue
-                out = arena_empty(total, dt, dev) if want_out else None
-                if want_out:
-                    outs[dt] = out
-                kind, data = self.routes[dt]
-                if kind == "flat":
-                    ins = ([center[dt]] if center is not None else []) + [data[i] for i in idx]
-                    _native.wreduce_dist(ins, weights, out, d2, accumulate=not first)
-                else:
-                    ptrs = []
-                    if center is not None:
-                        base = center[dt].data_ptr()
-                        ptrs += [base + o for o in layout.byte_offsets[dt]]
-                    for i in idx:
-                        ptrs += data[i]
-                    _native.wreduce_dist_tensors_raw(ptrs, m, layout.split_sizes[dt], layout.byte_offsets[dt],
-                                                     weights, None if out is None else out.data_ptr(),
-                                                     _native.dtype_code(dt, single_task=True), d2.data_ptr(),
-                                                     not first, raw_stream)
-                first = False
-            if first:
-                d2.zero_()
-        return outs, d2
-
-    def module(self, outs, to_host: Optional[bool]) -> nn.Module:
-        """copy.deepcopy(models[0]) around the arenas `outs` of a pass, on the
-        host when models[0] lives there (or to_host says so)."""
-        if self.host_out(to_host):
-            outs = arenas_to_host(outs, torch.cuda.current_stream(self.dev))  # waits for the stream
-        out = module_from_arenas(self.model0, self.layout, outs)
-        return _restride(out, self.layout) if self.staged else out
-
-
-def fp32_rounded(weights: Sequence[float]) -> List[float]:
-    """Every weight as the Python float of its fp32 rounding: what the fused
-    kernel is handed, for fp64 models too (trajectories are then reproducible
-    across dtypes)."""
-    return [float(np.float32(w)) for w in weights]
-
-
-def reduce_with_distances(models: List[nn.Module], weights: Sequence[float], device=None,
-                          to_host: Optional[bool] = None):
-    """(module, d2): the exact weighted reduce of `models` with `weights`
-    (rounded to fp32 first), as FedAvg.aggregate computes it, and the float64
-    host tensor of every model's squared L2 distance to that result over all
-    parameters: d2[i] = sum_e (double(x_i[e]) - double(out[e]))^2, from the
-    same pass over the models (dlsim_wreduce_dist). Buffers and
-    attributes are copy.deepcopy(models[0])'s; the module lives where models[0]
-    lives unless to_host says otherwise. The distances come back with one D2H
-    copy of n doubles, which waits for the stream."""
-    models[0]  # IndexError for an empty list, as the aggregators
-    assert len(weights) == len(models)
-    plan = ReduceDistPlan(models, device)
-    outs, d2 = plan.run(range(plan.n), fp32_rounded(weights))
-    host = d2.cpu()  # waits for the stream: the staged copies' sources may go now
-    return plan.module(outs, to_host), host
-
-
-def _copy_of_params(model0: nn.Module, layout: ParamLayout, params, views, dev: torch.device,
-                    host_out: bool) -> nn.Module:
-    """copy.deepcopy(model0) whose parameters hold `params`' values bit for
-    bit (a plain copy, not a 1-way reduce: x*0 + 1*x is not the identity for
-    Inf and NaN), in one arena per dtype on the host or on `dev`. views[dt]:
-    the model's flat arena of that dtype (one copy), or None (one per tensor)."""
-    arenas = {}
-    with torch.no_grad():
-        for dt, idx in layout.groups.items():
-            total = layout.totals[dt]
-            flat = torch.empty(total, dtype=dt) if host_out else arena_empty(total, dt, dev)
-            if views[dt] is not None:
-                flat.copy_(views[dt])
-            else:
-                for k in idx:
-                    off = layout.offsets[k]
-                    p = params[k]
-                    flat[off:off + p.numel()].copy_(p.detach().reshape(-1))
-            arenas[dt] = flat
-    return _restride(module_from_arenas(model0, layout, arenas), layout)
-
-
-def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Optional[bool] = None) -> nn.Module:
-    """Krum (m None) or Multi-Krum(m) of `models` with Byzantine count f
-    (gradient_aggregation/krum.py has the rule): the distance matrix on the
-    GPU (model_distances), the selection on the host, then Krum copies the
-    selected model's parameters bit for bit and Multi-Krum runs the selected
-    models, in ascending index order, through the exact weighted reduce with
-    float(1./m) each, as FedAvg.aggregate(selected) does. Buffers and
-    attributes are copy.deepcopy(models[0])'s; the result lives where
-    models[0] lives unless to_host says otherwise.
-
-    The selection needs the matrix on the host: one D2H copy of n*n doubles
-    and one stream synchronisation per call."""
-    from dasklearn_amd.gradient_aggregation import krum as _krum
-    model0 = models[0]  # IndexError for an empty list, as FedAvg
-    n = len(models)
-    _native.check_pairdist_fan_in(n)
-    _krum.check_krum_params(n, f, 1 if m is None else m)
-    d2 = model_distances(models)
-    chosen = _krum.krum_select(d2.tolist(), f, 1 if m is None else m)
-    p0 = module_params(model0)
-    host_out = (not any(p.is_cuda for p in p0)) if to_host is None else to_host
-    if m is None:
-        layout, all_params, in_views = input_arenas(models)
-        w = chosen[0]
-        views = {dt: None if v is None else v[w] for dt, v in in_views.items()}
-        return _copy_of_params(model0, layout, all_params[w], views, _target_device(all_params[0], None), host_out)
-    out = aggregate_modules([models[i] for i in chosen], None, _native.DLSIM_EXACT, to_host=host_out)
-    if chosen[0] == 0:
-        return out
-    # the reduce copied the first selected model's buffers and attributes:
-    # models[0]'s it must be, around the same parameters
-    memo = {}
-    for q0, q in zip(p0, module_params(out)):
-        q.requires_grad_(q0.requires_grad)
-        memo[id(q0)] = q
-    res = _clone_module(model0, memo)
-    entry = _arena_entry(out)
-    if entry is not None:
-        _register_arenas(res, entry)
-    return res
-
-
 def to_device_arena(model: nn.Module, device=None) -> nn.Module:
     """A copy of `model` (deepcopy semantics) whose parameters are views of one
     device arena per dtype — the form the aggregate reads in place. A plain
@@ -1771,3 +1448,13 @@ def to_device_arena(model: nn.Module, device=None) -> nn.Module:
                 flat[off:off + p.numel()].copy_(p.detach().reshape(-1), non_blocking=True)
             arenas[dt] = flat
     return module_from_arenas(model, layout, arenas)
+
+
+def __getattr__(name: str):
+    """The aggregates over n <= 32 models live in model_inputs.py (which imports this module); their
+    public names stay importable from here."""
+    if name in ("robust_modules", "model_distances", "krum_modules", "ReduceDistPlan", "reduce_with_distances",
+                "fp32_rounded"):
+        from . import model_inputs
+        return getattr(model_inputs, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

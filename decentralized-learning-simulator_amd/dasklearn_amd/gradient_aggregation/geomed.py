@@ -63,8 +63,8 @@ from typing import List, Optional, Sequence
 from torch import nn
 
 from dasklearn_amd import _native
-from dasklearn_amd.arena import ReduceDistPlan, fp32_rounded, reduce_with_distances
 from dasklearn_amd.gradient_aggregation import GradientAggregation
+from dasklearn_amd.model_inputs import ReduceDistPlan, fp32_rounded, reduce_with_distances
 
 aggregate_with_distances = reduce_with_distances  # public here, as krum.model_distances
 

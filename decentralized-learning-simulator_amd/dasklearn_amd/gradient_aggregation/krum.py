@@ -42,14 +42,9 @@ from typing import List, Optional, Sequence
 
 from torch import nn
 
-from dasklearn_amd.arena import krum_modules, model_distances  # noqa: F401  (model_distances: public here)
 from dasklearn_amd.gradient_aggregation import GradientAggregation
-
-
-def _check_unweighted(name: str, models, weights) -> None:
-    if weights:
-        assert len(weights) == len(models)
-        raise ValueError(f"{name} is unweighted: pass weights=None (got {len(weights)} weights)")
+from dasklearn_amd.gradient_aggregation.robust import _check_unweighted
+from dasklearn_amd.model_inputs import krum_modules, model_distances  # noqa: F401  (model_distances: public here)
 
 
 def check_krum_params(n: int, f: int, m: int = 1) -> None:

@@ -22,14 +22,14 @@ models, or a model whose parameter list differs from models[0]'s, ValueError.
 
 The arithmetic runs in one HIP kernel per dtype group
 (csrc/robust_kernels.hpp: an in-register sorting network per element) through
-dasklearn_amd.arena.robust_modules.
+dasklearn_amd.model_inputs.robust_modules.
 """
 from typing import List, Optional
 
 from torch import nn
 
-from dasklearn_amd.arena import robust_modules
 from dasklearn_amd.gradient_aggregation import GradientAggregation
+from dasklearn_amd.model_inputs import robust_modules
 
 
 def _check_unweighted(name: str, models, weights) -> None:
