@@ -273,9 +273,10 @@ def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Opt
     GPU (model_distances), the selection on the host, then Krum copies the
     selected model's parameters bit for bit and Multi-Krum runs the selected
     models, in ascending index order, through the exact weighted reduce with
-    float(1./m) each, as FedAvg.aggregate(selected) does. Buffers and
-    attributes are copy.deepcopy(models[0])'s; the result lives where
-    models[0] lives unless to_host says otherwise.
+    float(1./m) each, as FedAvg.aggregate(selected) does. Buffers,
+    attributes and parameter strides are copy.deepcopy(models[0])'s, also when
+    models[0] is not selected; the result lives where models[0] lives unless
+    to_host says otherwise.
 
     The selection needs the matrix on the host: one D2H copy of n*n doubles
     and one stream synchronisation per call."""
@@ -291,16 +292,22 @@ def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Opt
         w = chosen[0]
         views = {dt: None if v is None else v[w] for dt, v in inputs.in_views.items()}
         return _copy_of_params(model0, inputs.layout, inputs.all_params[w], views, inputs.dev, host_out)
+    params0 = inputs.layout.params
     del inputs  # the staged rows: the reduce below resolves the selected models for itself
     out = aggregate_modules([models[i] for i in chosen], None, _native.DLSIM_EXACT, to_host=host_out)
     if chosen[0] == 0:
         return out
-    # the reduce copied the first selected model's buffers and attributes:
-    # models[0]'s it must be, around the same parameters
+    # the reduce copied the first selected model's buffers, attributes and
+    # parameter strides: models[0]'s they must be, around the same values
     memo = {}
-    for q0, q in zip(module_params(model0), module_params(out)):
-        q.requires_grad_(q0.requires_grad)
-        memo[id(q0)] = q
+    with torch.no_grad():
+        for q0, q in zip(params0, module_params(out)):
+            q.requires_grad_(q0.requires_grad)
+            if q.stride() != q0.stride() and not (q.is_contiguous() and q0.is_contiguous()):
+                fresh = torch.empty_like(q0, memory_format=torch.preserve_format, device=q.device)
+                fresh.copy_(q.detach())
+                q.data = fresh  # leaves the result arena, as _restride's parameters do
+            memo[id(q0)] = q
     res = _clone_module(model0, memo)
     entry = _arena_entry(out)
     if entry is not None:

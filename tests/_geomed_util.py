@@ -144,10 +144,30 @@ def trajectory(rows, dtype: str, alphas, rule: str, iters: int, nu: float = 1e-6
     indices, fp32 `weights`, longdouble `exact` weights (None for pass 0),
     longdouble `d2` of the inputs of that pass (clip: the centre first) and
     the `tau` used."""
-    n = len(rows)
+    outs, passes = trajectory_groups([(rows, dtype)], alphas, rule, iters, nu=nu, tau=tau)
+    return outs[0], passes
+
+
+def _pass_over_groups(ins, dtypes, w):
+    """One pass over a model's dtype groups: every group folded by the FedAvg
+    oracle with the same weights, d2 the longdouble sum of the groups'
+    dist_oracle in that (layout) order."""
+    outs = [fold_oracle(x, w.astype(np.float64 if dt == "f64" else np.float32), dt) for x, dt in zip(ins, dtypes)]
+    with np.errstate(all="ignore"):
+        d2 = seq_sum(dist_oracle(x, o, dt) for x, o, dt in zip(ins, outs, dtypes))
+    return outs, d2
+
+
+def trajectory_groups(groups, alphas, rule: str, iters: int, nu: float = 1e-6, tau=None):
+    """trajectory() for models of several dtype groups: `groups` is the list of
+    (storage rows, dtype) of one model list in layout order, row i of every
+    group belonging to model i. Returns (final storage row per group, passes);
+    a model is kept when it is finite in every group."""
+    dtypes = [dt for _, dt in groups]
+    n = len(groups[0][0])
+    assert all(len(rows) == n for rows, _ in groups)
     alphas = [float(1. / n)] * n if not alphas else [float(a) for a in alphas]
-    wdt = np.float64 if dtype == "f64" else np.float32
-    kept = [i for i in range(n) if np.isfinite(eu.decode(np.asarray(rows[i]), dtype)).all()]
+    kept = [i for i in range(n) if all(np.isfinite(eu.decode(np.asarray(rows[i]), dt)).all() for rows, dt in groups)]
     if len(kept) in (0, n):
         w = np.asarray(alphas, dtype=np.float64).astype(np.float32)
         use = list(range(n))
@@ -155,12 +175,11 @@ def trajectory(rows, dtype: str, alphas, rule: str, iters: int, nu: float = 1e-6
         total = seq_sum(alphas[i] for i in kept)
         w = np.asarray([alphas[i] / total for i in kept], dtype=np.float64).astype(np.float32)
         use = kept
-    xs = [rows[i] for i in use]
-    out = fold_oracle(xs, w.astype(wdt), dtype)
-    d2 = dist_oracle(xs, out, dtype)
+    xs = [[rows[i] for i in use] for rows, _ in groups]
+    outs, d2 = _pass_over_groups(xs, dtypes, w)
     passes = [dict(kept=use, weights=w, exact=None, d2=d2, tau=None)]
     if not kept:
-        return out, passes
+        return outs, passes
     a = [alphas[i] for i in kept]
     if rule == "clip":
         total = seq_sum(a)
@@ -173,12 +192,11 @@ def trajectory(rows, dtype: str, alphas, rule: str, iters: int, nu: float = 1e-6
             w, t, ins = r32(exact), None, xs
         else:
             exact, t = ref_clip(d2, a, tau)
-            w, ins = r32(exact), [out] + xs
-        out = fold_oracle(ins, w.astype(wdt), dtype)
-        full = dist_oracle(ins, out, dtype)
+            w, ins = r32(exact), [[o] + x for o, x in zip(outs, xs)]
+        outs, full = _pass_over_groups(ins, dtypes, w)
         d2 = full if rule == "gm" else full[1:]
         passes.append(dict(kept=use, weights=w, exact=exact, d2=full, tau=t))
-    return out, passes
+    return outs, passes
 
 
 def separation_problems(passes, rule: str, numel: int, nu: float = 1e-6):
@@ -257,6 +275,38 @@ def case_inputs(case):
     rows, byz, _ = ku.separated_models(case["n"], case["f"], numel, "f32", seed=case["seed"], ms=(),
                                        nan_row=case["special"], inf_row=case["special"], byz=case["byz"])
     return rows, byz, dirichlet(case["n"], case["seed"]) if case["weighted"] else None
+
+
+# ---- two dtype groups through the whole iteration ----------------------------------------------
+# The `Mixed` module of the GPU tests: fp32 [33, 7] and [5], bf16 [129] and [4, 9]; layout order fp32, bf16.
+MIXED_GROUPS = (("f32", 33 * 7 + 5), ("bf16", 129 + 36))
+MIXED_NUMEL = sum(p for _, p in MIXED_GROUPS)
+# Seeds picked as CASES' were: the first from the start value whose trajectory passes separation_problems.
+MIXED_CASES = {
+    "gm-mixed-6": dict(rule="gm", n=6, f=1, seed=8600, tau=None),
+    "clip-mixed-6": dict(rule="clip", n=6, f=1, seed=8700, tau=None),
+}
+
+
+def mixed_case_trajectory(case):
+    """(groups [(storage rows, dtype) ...], Byzantine indices, final row per
+    group, passes) of a MIXED_CASES entry: separated_models' recipe (honest
+    rows base + 1e-2 noise, Byzantine rows base + N(0, 1)) over all 401
+    elements, split and rounded into the two groups."""
+    rng = np.random.default_rng(case["seed"])
+    n = case["n"]
+    base = rng.standard_normal(MIXED_NUMEL)
+    x = base[None, :] + 1e-2 * rng.standard_normal((n, MIXED_NUMEL))
+    byz = sorted(int(i) for i in rng.choice(n, size=case["f"], replace=False))
+    for i in byz:
+        x[i] = base + rng.standard_normal(MIXED_NUMEL)
+    groups, off = [], 0
+    for dt, p in MIXED_GROUPS:
+        groups.append((eu.encode(x[:, off:off + p], dt).reshape(n, p), dt))
+        off += p
+    iters = GM_ITERS if case["rule"] == "gm" else CLIP_ITERS
+    outs, passes = trajectory_groups(groups, None, case["rule"], iters, nu=GM_NU, tau=case["tau"])
+    return groups, byz, outs, passes
 
 
 def case_trajectory(case):

@@ -339,6 +339,30 @@ def test_separation_of_every_gpu_trajectory_input(name):
             assert (w < a * (1 - 1e-9)).any() and (np.abs(w - a) < 1e-12).any()
 
 
+@pytest.mark.parametrize("name", sorted(gu.MIXED_CASES))
+def test_separation_of_the_two_dtype_group_inputs(name):
+    """The same for the cases on the module with an fp32 and a bf16 group
+    (tests/test_gpu_model_routes.py): d2 is the sum of the groups' distances
+    over all 401 elements, and the separation is asked for that count."""
+    case = gu.MIXED_CASES[name]
+    groups, byz, outs, passes = gu.mixed_case_trajectory(case)
+    assert [(dt, rows.shape) for rows, dt in groups] == [("f32", (6, 236)), ("bf16", (6, 165))]
+    assert gu.MIXED_NUMEL == 401 and len(byz) == case["f"]
+    assert len(passes) == 1 + (gu.GM_ITERS if case["rule"] == "gm" else gu.CLIP_ITERS)
+    assert gu.separation_problems(passes, case["rule"], gu.MIXED_NUMEL, gu.GM_NU) == []
+    assert passes[0]["kept"] == list(range(case["n"]))
+    for (rows, dt), out in zip(groups, outs):
+        assert out.shape == (rows.shape[1],) and np.isfinite(eu.decode(out, dt)).all()
+    # one group alone through trajectory_groups is trajectory itself, and both groups contribute to d2
+    rows, dt = groups[0]
+    alone, alone_passes = gu.trajectory(list(rows), dt, None, case["rule"], 1, nu=gu.GM_NU, tau=case["tau"])
+    again, again_passes = gu.trajectory_groups([(rows, dt)], None, case["rule"], 1, nu=gu.GM_NU, tau=case["tau"])
+    assert np.array_equal(alone, again[0]) and np.array_equal(alone_passes[1]["d2"], again_passes[1]["d2"])
+    o32, o16 = (gu.fold_oracle(r, passes[0]["weights"], d) for r, d in groups)
+    want = gu.dist_oracle(groups[0][0], o32, "f32") + gu.dist_oracle(groups[1][0], o16, "bf16")
+    assert np.array_equal(passes[0]["d2"], want) and (passes[0]["d2"] > alone_passes[0]["d2"]).all()
+
+
 def test_the_geometric_median_of_the_oracle_is_closer_to_the_honest_mean():
     """The robustness claim the GPU test repeats on the kernel's result: with f
     far-away Byzantine rows the oracle's geometric median lies strictly closer
