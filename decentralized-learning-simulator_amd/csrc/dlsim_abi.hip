@@ -310,6 +310,9 @@ bool sgdm_cross_overlap(int t, const void* const* p, const void* const* g, const
 // inst_pairdist.hip, inst_reducedist.hip): arguments already checked.
 hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
                        hipStream_t st);
+hipError_t robust_batched(int b, const int* fan_in, const void* const* in, const int* lo, const int* hi,
+                          void* const* outs, const size_t* nelem, int dtype, hipStream_t st);
+size_t robust_batch_tile_elems(int n, int dtype);
 hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
                          hipStream_t st);
 void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
@@ -1196,6 +1199,66 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
     if (e != hipSuccess) return hip_fail(e, "robust reduce launch");
   }
   return DLSIM_OK;
+}
+
+int dlsim_robust_reduce_batched(int b, const int* fan_in, const void* const* d_inputs, const int* lo, const int* hi,
+                                void* const* d_outs, const size_t* n_elems, int dtype, void* stream) {
+  g_err.clear();
+  if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
+  if (b == 0) return DLSIM_OK;
+  if (!fan_in || !d_inputs || !lo || !hi || !d_outs || !n_elems) return fail(DLSIM_E_ARG, "null array argument");
+  const int rc = check_window_tasks(b, fan_in, d_inputs, lo, hi, d_outs, n_elems, DLSIM_MAX_ROBUST_INPUTS, dtype,
+                                    kRobustLimit);
+  if (rc != DLSIM_OK) return rc;
+  // the tasks are regrouped by capacity class: no order to promise, so any shared byte is refused
+  if (cross_task_overlap(b, fan_in, d_inputs, d_outs, n_elems, elem_bytes(dtype)))
+    return fail(DLSIM_E_ARG, "a task's output overlaps another task's input or output: the tasks of one call run in "
+                             "no promised order (use separate calls)");
+  const hipError_t e =
+      robust_batched(b, fan_in, d_inputs, lo, hi, d_outs, n_elems, dtype, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "robust reduce launch");
+}
+
+int dlsim_robust_batch_geometry(int n, int dtype, size_t* tile_elems, int* max_tasks, int* max_ptrs) {
+  g_err.clear();
+  const int rc = check_fan_in(n, DLSIM_MAX_ROBUST_INPUTS, dtype, kRobustLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!tile_elems || !max_tasks || !max_ptrs) return fail(DLSIM_E_ARG, "null result pointer");
+  *tile_elems = robust_batch_tile_elems(n, dtype);
+  *max_tasks = DLSIM_ROBUST_BATCH_MAX_TASKS;
+  *max_ptrs = DLSIM_ROBUST_BATCH_MAX_PTRS;
+  return DLSIM_OK;
+}
+
+int dlsim_robust_reduce_tensors_batched(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                        const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype,
+                                        void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_INPUTS, dtype, kRobustLimit);
+  if (rc == DLSIM_OK) rc = check_robust_window(n, lo, hi);
+  if (rc != DLSIM_OK || t == 0) return rc;
+  if (!d_inputs || !n_elems || !out_off_bytes) return fail(DLSIM_E_ARG, "null array argument");
+  rc = check_tensor_outputs(d_inputs, n, t, n_elems, d_out, out_off_bytes, elem_bytes(dtype));
+  if (rc != DLSIM_OK) return rc;
+  // every non-empty tensor is one task of fan-in n (task-major pointers)
+  std::vector<const void*> ins;
+  std::vector<void*> outs;
+  std::vector<size_t> lens;
+  ins.reserve(static_cast<size_t>(n) * t);
+  for (int k = 0; k < t; ++k) {
+    if (n_elems[k] == 0) continue;
+    ins.resize(ins.size() + static_cast<size_t>(n));
+    gather_row(d_inputs, n, t, k, ins.data() + ins.size() - static_cast<size_t>(n));
+    outs.push_back(static_cast<char*>(d_out) + out_off_bytes[k]);
+    lens.push_back(n_elems[k]);
+  }
+  const int b = static_cast<int>(lens.size());
+  if (b == 0) return DLSIM_OK;
+  const std::vector<int> fan(static_cast<size_t>(b), n), los(static_cast<size_t>(b), lo), his(static_cast<size_t>(b), hi);
+  const hipError_t e = robust_batched(b, fan.data(), ins.data(), los.data(), his.data(), outs.data(), lens.data(),
+                                      dtype, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "robust reduce launch");
 }
 
 int dlsim_pairwise_sqdist(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,

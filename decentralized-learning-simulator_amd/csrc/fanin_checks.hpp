@@ -51,6 +51,33 @@ inline int check_outputs_apart(int t, const void* base, const size_t* offs, cons
   return DLSIM_OK;
 }
 
+// The task list of dlsim_robust_reduce_batched: task t reads in[o_t .. o_t + fan_in[t]), o_t the
+// running sum of the fan-ins. Per task, in order: 1 <= fan_in <= max, 0 <= lo < hi <= fan_in, then
+// (non-empty tasks) a non-null output that shares no byte with the task's own inputs. The tasks
+// against each other are the caller's to check (cross_task_overlap, dispatch.hpp).
+inline int check_window_tasks(int b, const int* fan_in, const void* const* in, const int* lo, const int* hi,
+                              void* const* outs, const size_t* n_elems, int max, int dtype, const char* reason) {
+  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  const size_t esz = elem_bytes(dtype);
+  size_t off = 0;
+  for (int t = 0; t < b; ++t) {
+    const int n = fan_in[t];
+    if (n < 1) return fail(DLSIM_E_ARG, "task %d: n must be >= 1 (got %d)", t, n);
+    if (n > max) return fail(DLSIM_E_ARG, "task %d: n must be <= %d (got %d): %s", t, max, n, reason);
+    if (!(0 <= lo[t] && lo[t] < hi[t] && hi[t] <= n))
+      return fail(DLSIM_E_ARG, "task %d: the window must satisfy 0 <= lo < hi <= n (got lo %d, hi %d, n %d)", t,
+                  lo[t], hi[t], n);
+    if (n_elems[t] != 0) {
+      if (!outs[t]) return fail(DLSIM_E_ARG, "task %d: null output pointer", t);
+      const uintptr_t o0 = reinterpret_cast<uintptr_t>(outs[t]);
+      const int rc = check_inputs_apart(in + off, 1, n, n_elems[t] * esz, o0, o0 + n_elems[t] * esz, "output");
+      if (rc != DLSIM_OK) return fail(rc, "task %d: %s", t, std::string(g_err).c_str());
+    }
+    off += static_cast<size_t>(n);
+  }
+  return DLSIM_OK;
+}
+
 // row[i] = tensor k of model i, from the model-major in[i * t + k]
 inline void gather_row(const void* const* in, int n, int t, int k, const void** row) {
   for (int i = 0; i < n; ++i) row[i] = in[static_cast<size_t>(i) * static_cast<size_t>(t) + k];

@@ -207,9 +207,12 @@ __device__ __forceinline__ double rob_value(uint64_t u) { return __builtin_bit_c
 
 // ---- kernel arguments --------------------------------------------------------------
 // The n <= CAP input pointers travel in the kernarg segment (scalar loads).
+// ptr(i): the accessor every tile body reads its inputs through, so that a
+// batch's task view (robust_batch_kernels.hpp RobTaskArgs) runs the same code.
 template <int CAP>
 struct RobSlots {
   const void* p[CAP];
+  __device__ const void* ptr(int i) const { return p[i]; }
 };
 
 // s[lo] + s[lo+1] + ... + s[hi-1], seeded with s[lo], over CAP compile-time
@@ -229,13 +232,13 @@ __device__ __forceinline__ T rob_window(int lo, int hi, F&& value_at) {
 }
 
 // One element, any alignment (the < E tail and misaligned buffers).
-template <class Op, int CAP>
-__device__ __forceinline__ void rob_scalar_elem(const RobSlots<CAP>& s, int n, int lo, int hi, void* out, size_t j) {
+template <class Op, int CAP, class S>
+__device__ __forceinline__ void rob_scalar_elem(const S& s, int n, int lo, int hi, void* out, size_t j) {
   using SK = typename Op::SKey;
   decltype(rob_bits(acc_t<Op>{})) k[CAP];
 #pragma unroll
   for (int i = 0; i < CAP; ++i) {
-    if (i < n) k[i] = SK::to_key(rob_bits(load_elem<Op>(s.p[i], j)));
+    if (i < n) k[i] = SK::to_key(rob_bits(load_elem<Op>(s.ptr(i), j)));
     else k[i] = SK::kPad;
   }
   rob_sort<CAP>(k);
@@ -272,8 +275,8 @@ __device__ __forceinline__ void rob_sort_window(V (&k)[CAP], int lo, int hi, acc
 
 // One tile: lane's vectors v0 + k*kBlock; the loads of all n rows issue
 // before the first use (CAP * VPT * 4 VGPRs in flight per lane).
-template <class Op, int CAP, int VPT, bool CHECK, int STP>
-__device__ __forceinline__ void rob_tile(const RobSlots<CAP>& s, int n, int lo, int hi, const OutRef& out, size_t v0,
+template <class Op, int CAP, int VPT, bool CHECK, int STP, class S>
+__device__ __forceinline__ void rob_tile(const S& s, int n, int lo, int hi, const OutRef& out, size_t v0,
                                          size_t nvec) {
   using Key = typename Op::Key;
   using K = typename Op::K;
@@ -281,7 +284,7 @@ __device__ __forceinline__ void rob_tile(const RobSlots<CAP>& s, int n, int lo, 
   u32x4 r[CAP][VPT];
 #pragma unroll
   for (int i = 0; i < CAP; ++i)
-    if (i < n) load_tile<Op, VPT, 1, CHECK>(s.p[i], v0, nvec, r[i]);
+    if (i < n) load_tile<Op, VPT, 1, CHECK>(s.ptr(i), v0, nvec, r[i]);
   const float m = static_cast<float>(hi - lo);
 #pragma unroll
   for (int v = 0; v < VPT; ++v) {
@@ -330,8 +333,8 @@ __global__ __launch_bounds__(kBlock) void k_robust_tiles(const RobSlots<CAP> s, 
 // measurement). A wave still reads 512 contiguous bytes per row.
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-template <class Op, int CAP, bool CHECK>
-__device__ __forceinline__ void rob_half_tile(const RobSlots<CAP>& s, int n, int lo, int hi, void* out, size_t u0,
+template <class Op, int CAP, bool CHECK, class S>
+__device__ __forceinline__ void rob_half_tile(const S& s, int n, int lo, int hi, void* out, size_t u0,
                                               size_t nunit) {
   using Key = typename Op::Key;
   using K = typename Op::K;
@@ -341,7 +344,7 @@ __device__ __forceinline__ void rob_half_tile(const RobSlots<CAP>& s, int n, int
   for (int i = 0; i < CAP; ++i)
     if (i < n) {
       r[i] = u32x2{0u, 0u};
-      if (!CHECK || u0 < nunit) r[i] = __builtin_nontemporal_load(static_cast<const u32x2*>(s.p[i]) + u0);
+      if (!CHECK || u0 < nunit) r[i] = __builtin_nontemporal_load(static_cast<const u32x2*>(s.ptr(i)) + u0);
     }
   HV k[CAP];
 #pragma unroll

@@ -63,6 +63,9 @@ EXPORTS = (
     "dlsim_sgd_momentum_step_tensors",
     "dlsim_robust_reduce",
     "dlsim_robust_reduce_tensors",
+    "dlsim_robust_reduce_batched",
+    "dlsim_robust_batch_geometry",
+    "dlsim_robust_reduce_tensors_batched",
     "dlsim_pairwise_sqdist",
     "dlsim_pairwise_sqdist_tensors",
     "dlsim_pairdist_geometry",
@@ -204,6 +207,13 @@ def load() -> ctypes.CDLL:
         lib.dlsim_robust_reduce_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), ctypes.POINTER(sz),
                                                     i, i, vp, i, vp]
         lib.dlsim_robust_reduce_tensors.restype = i
+        lib.dlsim_robust_reduce_batched.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(vp), ctypes.POINTER(i),
+                                                    ctypes.POINTER(i), ctypes.POINTER(vp), ctypes.POINTER(sz), i, vp]
+        lib.dlsim_robust_reduce_batched.restype = i
+        lib.dlsim_robust_batch_geometry.argtypes = [i, i, ctypes.POINTER(sz), ctypes.POINTER(i), ctypes.POINTER(i)]
+        lib.dlsim_robust_batch_geometry.restype = i
+        lib.dlsim_robust_reduce_tensors_batched.argtypes = lib.dlsim_robust_reduce_tensors.argtypes
+        lib.dlsim_robust_reduce_tensors_batched.restype = i
         lib.dlsim_pairwise_sqdist.argtypes = [ctypes.POINTER(vp), i, sz, i, vp, i, vp]
         lib.dlsim_pairwise_sqdist.restype = i
         lib.dlsim_pairwise_sqdist_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), i, vp, i, vp]
@@ -571,6 +581,73 @@ def robust_reduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[i
            load().dlsim_robust_reduce_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
                                               _size_array(out_offsets), int(lo), int(hi), out_base, dtype,
                                               stream_handle))
+
+
+def robust_reduce_tensors_batched_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int],
+                                      out_offsets: Sequence[int], lo: int, hi: int, out_base: int, dtype: int,
+                                      stream_handle) -> None:
+    """dlsim_robust_reduce_tensors_batched, as robust_reduce_tensors_raw: every
+    non-empty tensor a task of one batched dispatch."""
+    check_robust_fan_in(n)
+    _check("dlsim_robust_reduce_tensors_batched",
+           load().dlsim_robust_reduce_tensors_batched(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
+                                                      _size_array(out_offsets), int(lo), int(hi), out_base, dtype,
+                                                      stream_handle))
+
+
+def _int_array(values):
+    return (ctypes.c_int * max(len(values), 1))(*[int(v) for v in values])
+
+
+def robust_reduce_batched_raw(fan_in: Sequence[int], in_ptrs: Sequence[int], los: Sequence[int],
+                              his: Sequence[int], out_ptrs: Sequence[int], numels: Sequence[int], dtype: int,
+                              stream_handle) -> None:
+    """dlsim_robust_reduce_batched on pointers the caller has already validated
+    (task-major: task t's fan_in[t] pointers follow task t-1's)."""
+    _check("dlsim_robust_reduce_batched",
+           load().dlsim_robust_reduce_batched(len(fan_in), _int_array(fan_in), _ptr_array(in_ptrs), _int_array(los),
+                                              _int_array(his), _ptr_array(out_ptrs), _size_array(numels), dtype,
+                                              stream_handle))
+
+
+def robust_reduce_batched(tasks, stream=None):
+    """dlsim_robust_reduce_batched: tasks = [(inputs, lo, hi, out)], each as
+    robust_reduce takes them (its exceptions too), all of one dtype on one
+    device; every task in a few shared launches, bit-identical to one
+    robust_reduce call each. No output may share memory with any input or
+    output of any task. Stream-ordered. Returns the outputs."""
+    if not tasks:
+        return []
+    dev, dt0 = tasks[0][3].device, tasks[0][3].dtype
+    fan, ptrs, los, his, outs, numels = [], [], [], [], [], []
+    for inputs, lo, hi, out in tasks:
+        n = len(inputs)
+        if n < 1:
+            raise IndexError("list index out of range")
+        check_robust_fan_in(n)
+        dt, numel = _check_flat_inputs(inputs, out, dev, "robust reduce")
+        if dt != dt0:
+            raise ValueError("one batched call takes tasks of one dtype")
+        fan.append(n)
+        ptrs += [t.data_ptr() for t in inputs]
+        los.append(lo)
+        his.append(hi)
+        outs.append(out.data_ptr())
+        numels.append(numel)
+    robust_reduce_batched_raw(fan, ptrs, los, his, outs, numels, dtype_code(dt0, single_task=True),
+                              _stream_handle(dev, stream))
+    return [t[3] for t in tasks]
+
+
+def robust_batch_geometry(n: int, torch_dtype):
+    """(tile_elems, max_tasks, max_ptrs) of dlsim_robust_batch_geometry: the
+    elements of one full tile of an aligned task of fan-in n in the batched
+    kernel, and the limits of one launch."""
+    tile, mt, mp = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0)
+    _check("dlsim_robust_batch_geometry",
+           load().dlsim_robust_batch_geometry(int(n), dtype_code(torch_dtype, single_task=True), ctypes.byref(tile),
+                                              ctypes.byref(mt), ctypes.byref(mp)))
+    return tile.value, mt.value, mp.value
 
 
 def pairwise_sqdist(inputs, out, accumulate: bool = False, stream=None):

@@ -30,14 +30,90 @@ def _resolve(models, weights) -> List[float]:
     return [float(w) for w in weights]
 
 
+def method_window(method, settings):
+    """lo_hi_fn (fan-in -> window [lo, hi)) of a batched method: MEDIAN, or
+    TRIMMED_MEAN with settings.aggregation_trim (default 1, as ModelManager);
+    None for every other method."""
+    from .gradient_aggregation import GradientAggregationMethod as M
+    from .gradient_aggregation.robust import median_window, trimmed_window
+    if method == M.MEDIAN:
+        return median_window
+    if method == M.TRIMMED_MEAN:
+        trim = int(getattr(settings, "aggregation_trim", 1))
+        if trim < 0:  # TrimmedMean.with_trim's check
+            raise ValueError(f"trim must be >= 0 (got {trim})")
+        return lambda n: trimmed_window(n, trim)
+    return None
+
+
+def check_window_task(method, window, models, weights) -> None:
+    """What CoordinateMedian / TrimmedMean raise for one task before they
+    touch the models: AssertionError or ValueError for weights, IndexError for
+    no model, ValueError for more than 32 or a trim that leaves no value."""
+    from .gradient_aggregation import GradientAggregationMethod as M
+    from .gradient_aggregation.robust import _check_unweighted
+    _check_unweighted("CoordinateMedian" if method == M.MEDIAN else "TrimmedMean", models, weights)
+    models[0]
+    _native.check_robust_fan_in(len(models))
+    window(len(models))
+
+
+def method_plugin(method, settings):
+    """The plugin class ModelManager picks for `method` (None for an unknown
+    value, as there), with `settings`' parameters."""
+    from .model_manager import ModelManager
+
+    class _Settings:  # `settings` (may be None) with the method set
+        gradient_aggregation = method
+
+        def __getattr__(self, name):
+            return getattr(settings, name)
+    return ModelManager(None, _Settings(), 0).get_aggregation_method()
+
+
+def _aggregate_batch_method(tasks, method, settings) -> List[nn.Module]:
+    """aggregate_batch for a method other than FedAvg."""
+    from .model_inputs import robust_arena_tasks
+    plugin = method_plugin(method, settings)
+    window = method_window(method, settings)
+    if window is None:
+        # Krum, Multi-Krum, geometric median, centered clipping (and an unknown
+        # value, which fails as the per-task path fails): the plugin per task,
+        # the result kept on the device
+        return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in tasks]
+    results: List[Optional[nn.Module]] = [None] * len(tasks)
+    prepared, where = [], []
+    for ti, (models, weights) in enumerate(tasks):
+        check_window_task(method, window, models, weights)
+        layout, _, views = input_arenas(models)  # ZipMismatch is a ValueError
+        if _device_views(views) is None:  # host models, separate tensors, several devices: the plugin stages them
+            results[ti] = plugin.aggregate(models, weights=None)
+            continue
+        prepared.append((models[0], layout, views, None))
+        where.append(ti)
+    for ti, out in zip(where, robust_arena_tasks(prepared, window)):
+        results[ti] = out
+    return results
+
+
 def aggregate_batch(tasks: Sequence[Tuple[List[nn.Module], Optional[Sequence[float]]]],
-                    mode: int = _native.DLSIM_EXACT) -> List[nn.Module]:
+                    mode: int = _native.DLSIM_EXACT, method=None, settings=None) -> List[nn.Module]:
     """tasks: [(models, weights)] -> one aggregated module per task.
 
     Tasks whose models are device-resident arenas (what this package returns
     for device inputs) are reduced together in batched launches; any other
     task goes through the single-task path. Output placement follows
-    FedAvg.aggregate (where models[0] lives)."""
+    FedAvg.aggregate (where models[0] lives).
+
+    method: a GradientAggregationMethod (None: FEDAVG), with its parameters
+    read from `settings` as ModelManager reads them. MEDIAN and TRIMMED_MEAN
+    batch their device-arena tasks through dlsim_robust_reduce_batched and
+    raise, per task, what their plugins raise; the other methods call their
+    plugin per task and keep the result on the device. `mode` applies to
+    FedAvg alone."""
+    from .gradient_aggregation import GradientAggregationMethod
+    if method is not None and method != GradientAggregationMethod.FEDAVG:
+        return _aggregate_batch_method(tasks, method, settings)
     results: List[Optional[nn.Module]] = [None] * len(tasks)
     prepared, where = [], []
     for ti, (models, weights) in enumerate(tasks):

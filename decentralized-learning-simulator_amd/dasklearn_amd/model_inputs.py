@@ -129,12 +129,84 @@ def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Opti
             if kind == "flat":
                 _native.robust_reduce(data, lo, hi, out)
             else:
-                _native.robust_reduce_tensors_raw([p for ptrs in data for p in ptrs], n, layout.split_sizes[dt],
-                                                  layout.byte_offsets[dt], lo, hi, out.data_ptr(),
-                                                  _native.dtype_code(dt, single_task=True), raw_stream)
+                # every tensor a sub-task of one batched dispatch, not a launch of its own
+                _native.robust_reduce_tensors_batched_raw([p for ptrs in data for p in ptrs], n,
+                                                          layout.split_sizes[dt], layout.byte_offsets[dt], lo, hi,
+                                                          out.data_ptr(), _native.dtype_code(dt, single_task=True),
+                                                          raw_stream)
         if not host_out and any(k is not None and len(k) for k in inputs.keep):
             torch.cuda.current_stream(dev).synchronize()  # the staged copies' sources may go now
     return inputs.module(outs, to_host)
+
+
+def robust_arena_tasks(prepared, lo_hi_fn, on_launched=None) -> List[nn.Module]:
+    """batch.aggregate_arena_tasks for the coordinate-wise order statistics:
+    the same `prepared` entries, (model0, layout of model0, {dtype: [flat arena
+    per model]}, weights (unused: these aggregates are unweighted)[, rows]),
+    every task's window [lo, hi) = lo_hi_fn(its fan-in), one
+    dlsim_robust_reduce_batched call per dtype and device over all tasks. A
+    dtype group whose arena list holds None is read from the models' separate
+    tensors in place (`rows`), one sub-task per tensor of the same call.
+    on_launched and the consumption of `prepared`: as aggregate_arena_tasks.
+    More than 32 models in a task raise ValueError before anything is queued."""
+    from .batch import _row_on, _rows_device
+    calls: Dict[tuple, list] = {}  # (dtype, device) -> [fan-ins, pointers, los, his, out pointers, lengths, keep]
+    outs = []
+    for entry in prepared:
+        model0, layout, views = entry[:3]
+        o = {}
+        for dt, vs in views.items():
+            n = len(vs)
+            _native.check_robust_fan_in(n)
+            lo, hi = lo_hi_fn(n)
+            total = layout.totals[dt]
+            in_place = any(v is None for v in vs)
+            dev = _rows_device(vs, entry[4], layout, dt) if in_place else vs[0].device
+            out = o[dt] = arena_empty(total, dt, dev)
+            if total == 0:
+                continue
+            c = calls.setdefault((dt, dev), [[], [], [], [], [], [], []])
+            if not in_place:
+                c[0].append(n)
+                c[1] += [v.data_ptr() for v in vs]
+                c[2].append(lo)
+                c[3].append(hi)
+                c[4].append(out.data_ptr())
+                c[5].append(total)
+                c[6].append(vs)
+                continue
+            idx, sizes, base = layout.groups[dt], layout.split_sizes[dt], out.data_ptr()
+            rows = [_row_on(entry[4][i], v, idx, sizes, dev) for i, v in enumerate(vs)]
+            for k, size, off in zip(idx, sizes, layout.byte_offsets[dt]):
+                if size == 0:
+                    continue
+                ts = [r[k] for r in rows]
+                for t in ts:
+                    if t.device != dev or t.dtype != dt or t.numel() != size or not t.is_contiguous():
+                        raise ValueError("rows input: tensors must be contiguous, of the layout's dtype and size, "
+                                         "on the task's device")
+                c[0].append(n)
+                c[1] += [t.data_ptr() for t in ts]
+                c[2].append(lo)
+                c[3].append(hi)
+                c[4].append(base + off)
+                c[5].append(size)
+            c[6].append(rows)
+        outs.append(o)
+    with torch.no_grad():
+        for (dt, dev), (fan, ptrs, los, his, out_ptrs, numels, _) in calls.items():
+            _native.robust_reduce_batched_raw(fan, ptrs, los, his, out_ptrs, numels,
+                                              _native.dtype_code(dt, single_task=True),
+                                              torch._C._cuda_getCurrentRawStream(dev.index))
+    calls.clear()
+    if on_launched is not None:
+        on_launched()
+    mods = []
+    for i, o in enumerate(outs):
+        model0, layout = prepared[i][:2]
+        prepared[i] = None
+        mods.append(module_from_arenas(model0, layout, o))
+    return mods
 
 
 def _distances(inputs: ModelInputs) -> torch.Tensor:

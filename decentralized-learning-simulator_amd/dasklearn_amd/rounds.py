@@ -19,7 +19,9 @@ anything else (host models, other devices) is copied once into a fresh arena
 (one concatenation, no module built). So an aggregate -> train ->
 aggregate chain never crosses PCIe when the train function works on the
 device. Results are bit-identical to running the same tasks one by one with
-FedAvg.aggregate.
+functions.aggregate under the same settings.gradient_aggregation: FedAvg, the
+median and the trimmed mean in batched launches, the other methods through
+their plugin task by task (RoundExecutor._aggregate_wave_method).
 """
 from __future__ import annotations
 
@@ -32,7 +34,10 @@ from torch import nn
 from . import _native
 from .arena import (ParamLayout, ZipMismatch, _target_device, aggregate_modules, aligned_empty, arena_empty, base_align,
                     layout_of, module_params, registered_arenas, row_stride)
-from .batch import _device_views, _resolve, aggregate_arena_tasks
+from .batch import _device_views, _resolve, aggregate_arena_tasks, check_window_task, method_window
+from .gradient_aggregation import GradientAggregationMethod
+from .model_inputs import robust_arena_tasks
+from .model_manager import ModelManager
 
 Task = Tuple[str, str, dict]  # (task_name, func_name, data with placeholders)
 
@@ -256,6 +261,9 @@ class RoundExecutor:
         see batch.aggregate_arena_tasks (the executor releases the results
         no later task reads there, so the input modules are freed while the
         output modules are built)."""
+        method = getattr(self.settings, "gradient_aggregation", GradientAggregationMethod.FEDAVG)
+        if method != GradientAggregationMethod.FEDAVG:
+            return self._aggregate_wave_method(aggs, method, on_launched)
         cache: dict = {}
         prepared = []
         resolved = []
@@ -290,6 +298,45 @@ class RoundExecutor:
             return outs
         it = iter(outs)
         return [single[j] if j in single else next(it) for j in range(n_tasks)]
+
+    def _aggregate_wave_method(self, aggs, method, on_launched=None) -> List[nn.Module]:
+        """The wave's aggregates under a method other than FedAvg, equal bit
+        for bit to functions.aggregate per task (ModelManager's plugins).
+        MEDIAN and TRIMMED_MEAN resolve the wave's models as the FedAvg path
+        does (one upload of the host models, arenas and separate device
+        tensors read in place) and run every task in one batched call per
+        dtype (model_inputs.robust_arena_tasks); each task raises what its
+        plugin raises. The other methods (and an unknown value, which fails
+        as the per-task path fails) call the plugin per task on the resolved
+        models and keep the result on the device."""
+        resolved = []
+        for name, _, data in aggs:
+            d = self._resolve(data)
+            resolved.append((d["models"], d.get("weights")))
+        window = method_window(method, self.settings)
+        if window is None:
+            plugin = ModelManager(None, self.settings, 0).get_aggregation_method()
+            return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in resolved]
+        for models, weights in resolved:
+            check_window_task(method, window, models, weights)
+        cache: dict = {}
+        walked: dict = {}
+        self._upload_host_models([m for models, _ in resolved for m in models], cache, walked)
+        prepared = []
+        for models, _ in resolved:
+            ents = [self._arena_of(m, cache, walked) for m in models]
+            layout0 = ents[0][0]
+            sig = layout0._signature
+            for i in range(1, len(ents)):
+                lay = ents[i][0]
+                if lay._signature is not sig and lay._signature != sig:
+                    layout0.check_compatible(models[i])  # ZipMismatch: a ValueError, as the plugins raise
+            views = {dt: [a[dt] for _, a in ents] for dt in layout0.groups}
+            prepared.append((models[0], layout0, views, None, [lay.params for lay, _ in ents]))
+        resolved.clear()
+        cache.clear()
+        walked.clear()
+        return robust_arena_tasks(prepared, window, on_launched)
 
     def run(self, tasks: Sequence[Task], seed: Optional[Dict[str, list]] = None) -> Dict[str, list]:
         """Execute `tasks`; `seed` pre-populates results (e.g. initial models).

@@ -661,6 +661,52 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
                                 const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype, void* stream);
 
 /*
+ * dlsim_robust_reduce_batched: b independent dlsim_robust_reduce tasks in a
+ * few launches (the medians or trimmed means of one simulated round's peers;
+ * DESIGN.md 8m). The order-statistic counterpart of dlsim_wreduce_batched.
+ *   fan_in    host array of b fan-ins, 1 <= fan_in[t] <= 32
+ *   d_inputs  host array of sum(fan_in) device pointers: task t reads
+ *             d_inputs[o_t .. o_t + fan_in[t]), o_t the running sum of the
+ *             fan-ins before it
+ *   lo, hi    host arrays of b windows, 0 <= lo[t] < hi[t] <= fan_in[t]
+ *   d_outs    host array of b output pointers; n_elems[t] elements each
+ *             (0 skips the task; b == 0 is a no-op)
+ * Each task follows dlsim_robust_reduce's contract and is bit-identical to
+ * it, for all four dtypes and any alignment. The tasks are regrouped by
+ * capacity class (fan-in up to 4, 8, 16, 32) and each class runs in launches
+ * of at most DLSIM_ROBUST_BATCH_MAX_TASKS tasks and
+ * DLSIM_ROBUST_BATCH_MAX_PTRS input pointers, so the call promises no order:
+ * no output may share a byte with any input or output of any task, its own
+ * included (DLSIM_E_ARG, decided for the whole list before the first launch
+ * and before any HIP call). A task with a pointer off a 16-byte boundary runs
+ * in the same launch, element by element; a task whose output exceeds one
+ * launch's byte limit (2 GiB - 1 MiB) runs alone, as dlsim_robust_reduce
+ * runs it. Stream-ordered; no allocation, no synchronisation.
+ */
+#define DLSIM_ROBUST_BATCH_MAX_TASKS 32
+#define DLSIM_ROBUST_BATCH_MAX_PTRS 192
+int dlsim_robust_reduce_batched(int b, const int* fan_in, const void* const* d_inputs, const int* lo, const int* hi,
+                                void* const* d_outs, const size_t* n_elems, int dtype, void* stream);
+
+/*
+ * dlsim_robust_batch_geometry: what a test needs to place task lengths on the
+ * batched kernel's edges. tile_elems: the elements of one full tile of a
+ * 16-byte aligned task of fan-in n (its capacity class) and this dtype;
+ * max_tasks, max_ptrs: the limits of one launch. Host only.
+ */
+int dlsim_robust_batch_geometry(int n, int dtype, size_t* tile_elems, int* max_tasks, int* max_ptrs);
+
+/*
+ * dlsim_robust_reduce_tensors_batched: dlsim_robust_reduce_tensors with every
+ * non-empty tensor a task of one dlsim_robust_reduce_batched dispatch (a
+ * handful of launches per model instead of one per tensor). Same arguments,
+ * same checks, same results bit for bit.
+ */
+int dlsim_robust_reduce_tensors_batched(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                        const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype,
+                                        void* stream);
+
+/*
  * dlsim_pairwise_sqdist: the matrix of squared L2 distances between n flat
  * buffers, the primitive under Krum and Multi-Krum and the consensus distance
  * of decentralized-learning papers.

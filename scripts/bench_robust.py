@@ -14,7 +14,22 @@ same bytes (for DESIGN.md §8j).
            the same buffers and rotation, in the same process, run before and
            after to show its own run-to-run spread
 
+  batch    (--batch, instead of the above) the batched entries
+           against the paths that were there before them, each leg in this one
+           process, the same rotation and decoy rule, a "launch" being one whole
+           call: (a) 100 tasks of n = 8 GNLeNet-sized fp32 rows: one
+           dlsim_robust_reduce_batched call against 100 dlsim_robust_reduce
+           calls, and against dlsim_wreduce_batched on the same buffers;
+           (b) n = 8 models in ResNet-18's 62 separate tensors:
+           dlsim_robust_reduce_tensors_batched against
+           dlsim_robust_reduce_tensors; (c) one RoundExecutor round of 100
+           GNLeNet peers with MEDIAN against the same tasks one by one through
+           functions.aggregate with aggregate_on_device (wall time, stream
+           synchronised); (d) one fp32 task of 11,181,642 elements, n = 8,
+           through the batched entry against the flat entry.
+
     python scripts/bench_robust.py [--windows 5] [--launches 200] [--skip-bf16]
+    python scripts/bench_robust.py --batch [--windows 5] [--legs abcd]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -122,14 +137,270 @@ def kernel_lines(P, tdt, n, launches, nwin):
     print(json.dumps(ratio), flush=True)
 
 
+# ---- the batched entries (--batch) ---------------------------------------------------------
+GNLENET_SHAPES = [(32, 3, 5, 5), (32,), (32,), (32,), (32, 32, 5, 5), (32,), (32,), (32,),
+                  (64, 32, 5, 5), (64,), (64,), (64,), (10, 576), (10,)]
+GNLENET_P = 85_354
+RESNET18_P = 11_181_642
+
+
+def resnet18_numels():
+    """Element counts of torchvision resnet18(num_classes=10)'s 62 parameters."""
+    shapes = [(64, 3, 7, 7), (64,), (64,)]
+    cin = 64
+    for cout, stride in ((64, 1), (128, 2), (256, 2), (512, 2)):
+        for b in range(2):
+            shapes += [(cout, cin, 3, 3), (cout,), (cout,), (cout, cout, 3, 3), (cout,), (cout,)]
+            if b == 0 and (stride != 1 or cin != cout):
+                shapes += [(cout, cin, 1, 1), (cout,), (cout,)]
+            cin = cout
+    return [int(np.prod(sh)) for sh in shapes + [(10, 512), (10,)]]
+
+
+class Call:
+    """One prepared library call (arguments resolved once); `keep` holds the tensors."""
+
+    def __init__(self, symbol, args, device, keep):
+        self.fn, self.symbol, self.args, self.device, self.keep = getattr(_native.load(), symbol), symbol, args, device, keep
+
+    def launch(self, stream=None):
+        rc = self.fn(*self.args, _native._stream_handle(self.device, stream))
+        if rc:
+            _native._check(self.symbol, rc)
+
+
+class Seq:
+    def __init__(self, plans):
+        self.plans = plans
+
+    def launch(self, stream=None):
+        for pl in self.plans:
+            pl.launch(stream)
+
+
+def batched_call(tasks, lo, hi):
+    """dlsim_robust_reduce_batched over tasks = [(inputs, out)], one window for all."""
+    b = len(tasks)
+    fan = (ctypes.c_int * b)(*[len(ins) for ins, _ in tasks])
+    ptrs = [t.data_ptr() for ins, _ in tasks for t in ins]
+    out = tasks[0][1]
+    args = (b, fan, (ctypes.c_void_p * len(ptrs))(*ptrs), (ctypes.c_int * b)(*[lo] * b), (ctypes.c_int * b)(*[hi] * b),
+            (ctypes.c_void_p * b)(*[o.data_ptr() for _, o in tasks]), (ctypes.c_size_t * b)(*[o.numel() for _, o in tasks]),
+            _native.dtype_code(out.dtype, single_task=True))
+    return Call("dlsim_robust_reduce_batched", args, out.device, tasks)
+
+
+def wreduce_batched_call(tasks):
+    """The yardstick of leg (a): dlsim_wreduce_batched, exact, uniform weights, the same buffers."""
+    b = len(tasks)
+    fan = (ctypes.c_int * b)(*[len(ins) for ins, _ in tasks])
+    ptrs = [t.data_ptr() for ins, _ in tasks for t in ins]
+    w = np.concatenate([np.full(len(ins), 1.0 / len(ins), dtype=np.float32) for ins, _ in tasks])
+    out = tasks[0][1]
+    args = (b, fan, (ctypes.c_void_p * len(ptrs))(*ptrs), w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            (ctypes.c_void_p * b)(*[o.data_ptr() for _, o in tasks]), (ctypes.c_size_t * b)(*[o.numel() for _, o in tasks]),
+            _native.dtype_code(out.dtype), _native.DLSIM_EXACT)
+    return Call("dlsim_wreduce_batched", args, out.device, (tasks, w))
+
+
+def tensors_call(symbol, models, numels, offs_bytes, lo, hi, out):
+    """dlsim_robust_reduce_tensors[_batched]: models = [[tensor per parameter] per model]."""
+    n, t = len(models), len(numels)
+    ptrs = [x.data_ptr() for m in models for x in m]
+    args = ((ctypes.c_void_p * len(ptrs))(*ptrs), n, t, (ctypes.c_size_t * t)(*numels), (ctypes.c_size_t * t)(*offs_bytes),
+            lo, hi, ctypes.c_void_p(out.data_ptr()), _native.dtype_code(out.dtype, single_task=True))
+    return Call(symbol, args, out.device, (models, out))
+
+
+def report(base, leg, ws, **extra):
+    print(json.dumps(dict(base, leg=leg, median_us=round(ws[len(ws) // 2], 3), min_us=round(ws[0], 3),
+                          max_us=round(ws[-1], 3), **extra)), flush=True)
+    return ws[len(ws) // 2]
+
+
+def filled(count, P, tdt, dev, seed):
+    """count rows of P elements at the arena row stride, normal * 0.05."""
+    esz = torch.empty((), dtype=tdt).element_size()
+    stride = row_stride(P, esz)
+    rows = aligned_empty(count * stride, tdt, dev, base_align(P * esz, esz)).view(count, stride)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    for i in range(count):
+        rows[i, :P].copy_((torch.randn(P, generator=g, device=dev) * 0.05).to(tdt))
+    return [rows[i, :P] for i in range(count)]
+
+
+def ratio_line(base, leg, res, num, den, yards):
+    spread = (max(yards) - min(yards)) / (sum(yards) / len(yards))
+    print(json.dumps(dict(base, leg=leg, **{f"{num}_over_{den}": round(res[num] / res[den], 4)},
+                          yardstick_spread=round(spread, 4))), flush=True)
+
+
+def leg_a(nwin, launches):
+    """100 tasks x n = 8 x GNLeNet-sized fp32 rows (a 100-peer round, every peer reading 8 of the 100 models)."""
+    dev, b, n, P = torch.device("cuda", 0), 100, 8, GNLENET_P
+    sets = -(-(1 << 30) // (b * P * 4)) + 1  # >= 1 GiB of distinct inputs, + the decoy
+    out_sets = -(-(1 << 30) // (b * P * 4))
+    out_sets = -(-out_sets // (sets - 1)) * (sets - 1)
+    models = [filled(b, P, torch.float32, dev, s) for s in range(sets)]
+    outs = [[arena_empty(P, torch.float32, dev) for _ in range(b)] for _ in range(out_sets + 1)]
+    med = ((n - 1) // 2, (n - 1) // 2 + 1)
+
+    def tasks(s, j):
+        return [([models[s][(p + d) % b] for d in range(n)], outs[j][p]) for p in range(b)]
+    decoy = batched_call(tasks(sets - 1, out_sets), *med)
+    for _ in range(8):
+        decoy.launch()
+    torch.cuda.synchronize()
+    base = {"bench": "robust_batch", "case": "a", "tasks": b, "n": n, "params": P, "dtype": "float32", "window": list(med),
+            "bytes": (n + 1) * P * 4 * b, "rotating_sets": sets - 1, "rotating_outputs": out_sets,
+            "calls_per_window": launches, "windows": nwin}
+    res, yards = {}, []
+    for leg in ("per_task_1", "batched", "wreduce_batched", "per_task_2"):
+        plans = []
+        for j in range(out_sets):
+            tk = tasks(j % (sets - 1), j)
+            if leg == "batched":
+                plans.append(batched_call(tk, *med))
+            elif leg == "wreduce_batched":
+                plans.append(wreduce_batched_call(tk))
+            else:
+                plans.append(Seq([RobustPlan(ins, *med, out) for ins, out in tk]))
+        ws = windows(plans, launches, nwin)
+        res[leg] = report(base, leg, ws, us_per_task=round(ws[len(ws) // 2] / b, 3),
+                          GBps=round(base["bytes"] / ws[len(ws) // 2] / 1e3, 1))
+        if leg.startswith("per_task"):
+            yards.append(res[leg])
+    res["per_task"] = sum(yards) / 2
+    ratio_line(base, "ratio", res, "batched", "per_task", yards)
+    ratio_line(base, "ratio_fedavg", res, "batched", "wreduce_batched", yards)
+
+
+def leg_b(nwin, launches):
+    """n = 8 models whose parameters are ResNet-18's 62 separate tensors, into one output arena."""
+    dev, n, numels = torch.device("cuda", 0), 8, resnet18_numels()
+    P = sum(numels)
+    assert P == RESNET18_P and len(numels) == 62
+    offs = [int(o) * 4 for o in np.concatenate([[0], np.cumsum(numels)])[:-1]]  # an arena's byte offsets
+    sets = max(3, -(-(1 << 30) // (n * P * 4))) + 1
+    out_sets = -(-(-(-(1 << 30) // (P * 4))) // (sets - 1)) * (sets - 1)
+    g = torch.Generator(device=dev).manual_seed(1)
+    # every tensor its own allocation, as a device model's parameters are
+    models = [[[(torch.randn(k, generator=g, device=dev) * 0.05) for k in numels] for _ in range(n)] for _ in range(sets)]
+    outs = [arena_empty(P, torch.float32, dev) for _ in range(out_sets + 1)]
+    med = (3, 4)
+    decoy = tensors_call("dlsim_robust_reduce_tensors_batched", models[sets - 1], numels, offs, *med, outs[out_sets])
+    for _ in range(8):
+        decoy.launch()
+    torch.cuda.synchronize()
+    base = {"bench": "robust_batch", "case": "b", "tensors": len(numels), "n": n, "params": P, "dtype": "float32",
+            "window": list(med), "bytes": (n + 1) * P * 4, "rotating_sets": sets - 1, "rotating_outputs": out_sets,
+            "calls_per_window": launches, "windows": nwin}
+    res, yards = {}, []
+    for leg, symbol in (("per_tensor_1", "dlsim_robust_reduce_tensors"), ("batched", "dlsim_robust_reduce_tensors_batched"),
+                        ("per_tensor_2", "dlsim_robust_reduce_tensors")):
+        plans = [tensors_call(symbol, models[j % (sets - 1)], numels, offs, *med, outs[j]) for j in range(out_sets)]
+        ws = windows(plans, launches, nwin)
+        res[leg] = report(base, leg, ws, GBps=round(base["bytes"] / ws[len(ws) // 2] / 1e3, 1))
+        if leg.startswith("per_tensor"):
+            yards.append(res[leg])
+    res["per_tensor"] = sum(yards) / 2
+    ratio_line(base, "ratio", res, "batched", "per_tensor", yards)
+
+
+def leg_c(nwin):
+    """One round of 100 GNLeNet peers, every peer the median of 8 device arenas: RoundExecutor against the same
+    tasks one by one through functions.aggregate (aggregate_on_device). Wall time of the round, stream synchronised."""
+    import time
+    import types
+
+    from torch import nn
+
+    from dasklearn_amd import arena, functions
+    from dasklearn_amd.gradient_aggregation import GradientAggregationMethod
+    from dasklearn_amd.rounds import RoundExecutor
+
+    class Shaped(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.ps = nn.ParameterList([nn.Parameter(torch.randn(*sh) * 0.05) for sh in GNLENET_SHAPES])
+    peers, n = 100, 8
+    torch.manual_seed(0)
+    pool = [arena.to_device_arena(Shaped(), "cuda") for _ in range(peers)]
+    settings = types.SimpleNamespace(gradient_aggregation=GradientAggregationMethod.MEDIAN, aggregate_on_device=True)
+    tasks = [(f"agg_{p}", "aggregate", {"models": [(f"m_{(p + d) % peers}", 0) for d in range(n)], "round": 1, "peer": p})
+             for p in range(peers)]
+
+    def executor():
+        ex = RoundExecutor({}, settings, keep_all=True)
+        return ex.run(tasks, seed={f"m_{p}": [pool[p]] for p in range(peers)})
+
+    def per_task():
+        return [functions.aggregate(settings, {"models": [pool[(p + d) % peers] for d in range(n)], "round": 1, "peer": p})
+                for p in range(peers)]
+    base = {"bench": "robust_batch", "case": "c", "peers": peers, "n": n, "params": GNLENET_P, "dtype": "float32",
+            "method": "MEDIAN", "timing": "wall, synchronised", "reps": nwin}
+    res, yards = {}, []
+    for leg, fn in (("per_task_1", per_task), ("executor", executor), ("per_task_2", per_task)):
+        fn()
+        torch.cuda.synchronize()
+        ws = []
+        for _ in range(nwin):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ws.append((time.perf_counter() - t0) * 1e6)
+        ws.sort()
+        res[leg] = report(base, leg, ws, us_per_task=round(ws[len(ws) // 2] / peers, 2))
+        if leg.startswith("per_task"):
+            yards.append(res[leg])
+    res["per_task"] = sum(yards) / 2
+    ratio_line(base, "ratio", res, "executor", "per_task", yards)
+
+
+def leg_d(nwin, launches):
+    """One fp32 task of 11,181,642 elements, n = 8, alone in a batched call: what the run-time fan-in and the
+    descriptor lookup cost against the flat entry."""
+    dev, n, P = torch.device("cuda", 0), 8, RESNET18_P
+    sets = max(3, -(-(1 << 30) // (n * P * 4))) + 1
+    out_sets = -(-(-(-(1 << 30) // (P * 4))) // (sets - 1)) * (sets - 1)
+    ins = [filled(n, P, torch.float32, dev, s) for s in range(sets)]
+    outs = [arena_empty(P, torch.float32, dev) for _ in range(out_sets + 1)]
+    med = (3, 4)
+    decoy = RobustPlan(ins[sets - 1], *med, outs[out_sets])
+    for _ in range(8):
+        decoy.launch()
+    torch.cuda.synchronize()
+    base = {"bench": "robust_batch", "case": "d", "tasks": 1, "n": n, "params": P, "dtype": "float32", "window": list(med),
+            "bytes": (n + 1) * P * 4, "rotating_sets": sets - 1, "rotating_outputs": out_sets,
+            "calls_per_window": launches, "windows": nwin}
+    res, yards = {}, []
+    for leg in ("flat_1", "batched", "flat_2"):
+        plans = [batched_call([(ins[j % (sets - 1)], outs[j])], *med) if leg == "batched" else
+                 RobustPlan(ins[j % (sets - 1)], *med, outs[j]) for j in range(out_sets)]
+        ws = windows(plans, launches, nwin)
+        res[leg] = report(base, leg, ws, GBps=round(base["bytes"] / ws[len(ws) // 2] / 1e3, 1))
+        if leg.startswith("flat"):
+            yards.append(res[leg])
+    res["flat"] = sum(yards) / 2
+    ratio_line(base, "ratio", res, "batched", "flat", yards)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--skip-bf16", action="store_true")
+    ap.add_argument("--batch", action="store_true", help="the batched entries' legs (a)-(d) instead of the flat kernel's")
+    ap.add_argument("--legs", default="abcd", help="with --batch: which of the legs a, b, c, d")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_robust.py measures on a GPU; none is visible")
+    if a.batch:
+        for leg in a.legs:
+            {"a": lambda: leg_a(a.windows, 20), "b": lambda: leg_b(a.windows, 40), "c": lambda: leg_c(a.windows),
+             "d": lambda: leg_d(a.windows, a.launches)}[leg]()
+            torch.cuda.empty_cache()
+        return
     for n in (4, 8, 16, 32):
         kernel_lines(11_181_642, torch.float32, n, a.launches, a.windows)
         torch.cuda.empty_cache()

@@ -42,6 +42,11 @@ shapes, dtypes, alignments, weights and special values, for a time budget.
               dtype (all four), size, alignment of every input and of the
               output, special values, vs tests/_robust_util.py's restatement of
               the contract
+  robust_batch  dlsim_robust_reduce_batched and dlsim_robust_reduce_tensors_batched
+              (DESIGN.md §8m): 1..40 tasks of random fan-in 1..32 (all
+              capacity classes in one call), window, size (empty ones too) and
+              alignment of every buffer, one dtype (all four) per call, vs the
+              same restatement per task; then one model as separate tensors
 
 Prints one JSON line with the case counts and the first failures (if any).
 
@@ -517,6 +522,53 @@ def robust_case(rng, dtype):
     return ok, dict(kind="robust", dtype=dtype, n=n, lo=lo, hi=hi, sizes=sizes)
 
 
+def robust_batch_case(rng, dtype):
+    """The batched order-statistic entries against the CPU restatement of the
+    contract per task, bit for bit."""
+    import _robust_util as ru
+    dt = DT[dtype]
+
+    def dev(x):
+        off = int(rng.choice([0, 0, 0, 1, 3]))
+        buf = torch.empty(x.numel() + off, dtype=dt, device="cuda")
+        buf[off:].copy_(x)
+        return buf[off:]
+    b = int(rng.choice([1, 2, 5, 33, int(rng.integers(1, 41))]))
+    tasks, exps, budget = [], [], 3_000_000
+    for _ in range(b):
+        n = int(rng.choice([1, 3, 4, 5, 8, 9, 16, 17, 32, int(rng.integers(1, 33))]))
+        lo = int(rng.integers(0, n))
+        hi = int(rng.integers(lo + 1, n + 1))
+        p = int(rng.choice([0, 1, 2, 7, 8, 9, 255, 256, 257, 1025, 4099, 8193, 65537]))
+        if n * p > budget:
+            p = 4099
+        budget -= n * p
+        xs = ru.random_rows(dt, n, p, int(rng.integers(0, 1 << 31)), special_frac=float(rng.choice([0.0, 0.02, 0.3]))) \
+            if p else [torch.empty(0, dtype=dt)] * n
+        exps.append(ru.window_mean(xs, lo, hi) if p else None)
+        tasks.append(([dev(x) for x in xs], lo, hi, dev(torch.zeros(p, dtype=dt))))
+    _native.robust_reduce_batched(tasks)
+    ok = all(e is None or ru.same_bits(t[3].cpu(), e) for t, e in zip(tasks, exps))
+    # one model as separate tensors, into one output arena
+    n = int(rng.integers(1, 33))
+    lo = int(rng.integers(0, n))
+    hi = int(rng.integers(lo + 1, n + 1))
+    sizes = [int(rng.choice([0, 1, 7, 10, 64, 1025, 4099, 20_001])) for _ in range(int(rng.integers(1, 40)))]
+    total = sum(sizes)
+    xs = ru.random_rows(dt, n, total, int(rng.integers(0, 1 << 31))) if total else [torch.empty(0, dtype=dt)] * n
+    offs = [int(o) for o in np.concatenate([[0], np.cumsum(sizes)])[:-1]]
+    parts = [[dev(x[o:o + k]) for o, k in zip(offs, sizes)] for x in xs]
+    out = dev(torch.zeros(total, dtype=dt))
+    esz = out.element_size()
+    _native.robust_reduce_tensors_batched_raw([t.data_ptr() for row in parts for t in row], n, sizes,
+                                              [o * esz for o in offs], lo, hi, out.data_ptr(),
+                                              _native.dtype_code(dt, single_task=True),
+                                              torch.cuda.current_stream().cuda_stream)
+    ok = ok and (not total or ru.same_bits(out.cpu(), ru.window_mean(xs, lo, hi)))
+    return ok, dict(kind="robust_batch", dtype=dtype, tasks=b, fan_ins=[len(t[0]) for t in tasks],
+                    sizes=[t[3].numel() for t in tasks], tensors_n=n, tensors=sizes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
@@ -527,7 +579,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     counts = {"reduce": 0, "reduce_fast": 0, "tensors": 0, "batched": 0, "chunk_mean": 0, "modules": 0,
               "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0, "sgdm": 0,
-              "robust": 0}
+              "robust": 0, "robust_batch": 0}
     fails = []
     t_end = time.time() + a.seconds
     t_note = time.time() + 20
@@ -537,13 +589,15 @@ def main():
             t_note = time.time() + 20
         dtype = str(rng.choice(["f32", "bf16", "f16", "f64"]))
         which = rng.choice(["reduce", "tensors", "batched", "chunk_mean", "modules", "reconstruct",
-                            "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd", "sgdm", "robust"],
-                           p=[0.085, 0.085, 0.085, 0.085, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.08, 0.08, 0.06])
+                            "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd", "sgdm", "robust",
+                            "robust_batch"],
+                           p=[0.085, 0.085, 0.085, 0.085, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.07, 0.07, 0.04, 0.04])
         if only:
             which = str(rng.choice(only))
         if which in ("sgd", "sgdm") and dtype == "f16":
             dtype = "f32"  # fp16 has no SGD-step kernel (torch's CPU ops run it)
-        if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd", "sgdm", "robust"):
+        if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd", "sgdm", "robust",
+                                                 "robust_batch"):
             dtype = "f32"  # fp64 reduces are the single-task entry (dlsim_wreduce_f64); chunk means take fp64
         try:
             if which == "reduce":
@@ -765,6 +819,9 @@ def main():
             elif which == "robust":
                 ok, case = robust_case(rng, dtype)
                 counts["robust"] += 1
+            elif which == "robust_batch":
+                ok, case = robust_batch_case(rng, dtype)
+                counts["robust_batch"] += 1
             elif which == "host_chunk":
                 from dasklearn_amd.arena import _side_streams
                 cpu_threads = int(rng.choice([1, 2, 4, 8, 16]))
