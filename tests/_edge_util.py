@@ -421,20 +421,24 @@ def expected_reduce(op: str, rows, w, dtype: str) -> np.ndarray:
 
 
 def reduce_case(op: str, dtype: str, rows, w, device, out_offset: int = 0, in_offsets=None, alias: bool = False,
-                expected=None):
+                expected=None, alias_index: int = 0):
     """_native.wreduce (op "exact" / "fast") or _native.mean (op "mean") of the
     storage rows into a guarded output `out_offset` bytes off alignment
-    (inputs: `in_offsets` bytes each; alias: the output is input 0). Returns
+    (inputs: `in_offsets` bytes each; alias: the output is input `alias_index`,
+    and `in_offsets` are those of the other inputs, in order). Returns
     the list of problems found, empty when the guards are clean, the view
     equals the oracle bit for bit and no other input changed."""
     from dasklearn_amd import _native
     rows = np.asarray(rows)
     n, p = rows.shape
+    assert 0 <= alias_index < n
     h = guarded(p * ESIZE[dtype], dtype, device, offset=out_offset)
-    xs = place(list(rows[1:] if alias else rows), dtype, device, in_offsets)
+    others = [i for i in range(n) if not (alias and i == alias_index)]
+    xs = place([rows[i] for i in others], dtype, device, in_offsets)
+    kept = list(xs)  # the separately placed inputs, rows[others]: what must not change
     if alias:
-        h.view.copy_(to_torch(rows[0], dtype))
-        xs = [h.view] + xs
+        h.view.copy_(to_torch(rows[alias_index], dtype))
+        xs.insert(alias_index, h.view)
     if op == "mean":
         _native.mean(xs, h.view)
     else:
@@ -448,7 +452,7 @@ def reduce_case(op: str, dtype: str, rows, w, device, out_offset: int = 0, in_of
     got = from_torch(h.view, dtype)
     if not same_bits(got, exp, dtype):
         problems.append(f"differs from the oracle ({unwritten(h)} elements unwritten): " + diff_report(got, exp, dtype))
-    if not inputs_unchanged(xs[1:] if alias else xs, rows[1:] if alias else rows, dtype):
+    if not inputs_unchanged(kept, [rows[i] for i in others], dtype):
         problems.append("an input changed")
     return problems
 

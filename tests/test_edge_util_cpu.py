@@ -122,6 +122,68 @@ def test_inputs_unchanged_sees_one_changed_byte():
     assert not eu.inputs_unchanged(devs, rows, "bf16")
 
 
+# ---- reduce_case's bookkeeping, on a fake kernel ------------------------------------------------
+def _fake_native(monkeypatch, spoil=None):
+    """_native.wreduce replaced by the oracle's fold of the tensors it is given,
+    in the order it is given them, stored to `out` once every input is read (as
+    the ABI allows out == inputs[i]); spoil: an input position it then
+    overwrites with ones. Returns the list the calls are recorded in."""
+    from dasklearn_amd import _native
+    calls = []
+
+    def wreduce(xs, w, out, mode=_native.DLSIM_EXACT):
+        calls.append(([x.data_ptr() for x in xs], out.data_ptr()))
+        res = orc.wreduce_rows_f32(np.stack([eu.from_torch(x, "f32") for x in xs]), w)
+        out.copy_(eu.to_torch(res, "f32"))
+        if spoil is not None:
+            xs[spoil].fill_(1.0)
+
+    monkeypatch.setattr(_native, "wreduce", wreduce)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: None)
+    return calls
+
+
+def _alias_case(n=5, p=37):
+    rows = eu.special_rows("f32", n, p, (0,), seed=9)
+    return rows, eu.special_weights(n, "dirichlet", "f32")  # five different weights: the order matters
+
+
+@pytest.mark.parametrize("alias_index", [0, 1, 4])
+def test_reduce_case_puts_the_aliased_output_at_alias_index(monkeypatch, alias_index):
+    calls = _fake_native(monkeypatch)
+    rows, w = _alias_case()
+    assert eu.reduce_case("exact", "f32", rows, w, CPU, alias=True, alias_index=alias_index) == []
+    (ins, out), = calls
+    assert len(ins) == 5 and ins.index(out) == alias_index and ins.count(out) == 1
+    # the other inputs in their order: the same rows folded in any other order differ
+    moved = np.roll(rows, 1, axis=0)
+    assert not orc.same_bits(orc.wreduce_rows_f32(moved, w), orc.wreduce_rows_f32(rows, w))
+    assert eu.reduce_case("exact", "f32", rows, w, CPU, alias=True, alias_index=alias_index,
+                          expected=orc.wreduce_rows_f32(moved, w)) != []
+
+
+def test_reduce_case_alias_defaults_to_input_0_and_no_alias_ignores_the_index(monkeypatch):
+    calls = _fake_native(monkeypatch)
+    rows, w = _alias_case()
+    assert eu.reduce_case("exact", "f32", rows, w, CPU, alias=True) == []
+    assert eu.reduce_case("exact", "f32", rows, w, CPU) == []
+    assert eu.reduce_case("exact", "f32", rows, w, CPU, alias_index=3) == []
+    (a_ins, a_out), (b_ins, b_out), (c_ins, c_out) = calls
+    assert a_ins[0] == a_out and b_out not in b_ins and c_out not in c_ins
+
+
+@pytest.mark.parametrize("alias_index", [0, 2, 4])
+def test_reduce_case_reports_a_changed_input_but_not_the_aliased_one(monkeypatch, alias_index):
+    rows, w = _alias_case()
+    for spoil in range(5):
+        _fake_native(monkeypatch, spoil=spoil)
+        found = eu.reduce_case("exact", "f32", rows, w, CPU, alias=True, alias_index=alias_index)
+        if spoil == alias_index:  # the output itself: the view no longer equals the oracle
+            assert found and all("input changed" not in f for f in found)
+        else:
+            assert found == ["an input changed"]
+
+
 @pytest.mark.parametrize("dtype", ALL_DTYPES)
 def test_generators_never_produce_the_fill_pattern(dtype):
     fill = eu.fill_pattern(dtype)
@@ -168,7 +230,7 @@ def test_default_small_shape_is_two_tiles_a_partial_tile_and_a_tail():
 
 # ---- the reference-only pre-check -------------------------------------------------------------
 # every fan-in the GPU edge tests use (tests/test_gpu_edges_*.py)
-EDGE_FAN_INS = (1, 2, 3, 4, 8, 9, 14, 15, 16, 17, 128, 129)
+EDGE_FAN_INS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 128, 129)
 
 
 def _col(names, prefix):
