@@ -307,7 +307,7 @@ bool sgdm_cross_overlap(int t, const void* const* p, const void* const* g, const
 }
 
 // The dispatches of the entries over n <= 32 inputs (inst_robust.hip,
-// inst_pairdist.hip, inst_reducedist.hip): arguments already checked.
+// inst_pairdist.hip, inst_pairdist_batch.hip, inst_reducedist.hip): arguments already checked.
 hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
                        hipStream_t st);
 hipError_t robust_batched(int b, const int* fan_in, const void* const* in, const int* lo, const int* hi,
@@ -316,6 +316,8 @@ size_t robust_batch_tile_elems(int n, int dtype);
 hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
                          hipStream_t st);
 void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
+hipError_t pairdist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* in,
+                            const size_t* nelem, int dtype, double* const* d2s, int accumulate, hipStream_t st);
 hipError_t reducedist_flat(const void* const* in, int n, const double* w, void* out, size_t nelem, int dtype,
                            double* d2, int accumulate, hipStream_t st);
 void reducedist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
@@ -1311,6 +1313,31 @@ int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems
   if (rc != DLSIM_OK) return rc;
   if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
   pairdist_geometry(n, dtype, n_elems, tile_elems, blocks);
+  return DLSIM_OK;
+}
+
+int dlsim_pairwise_sqdist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* d_inputs,
+                                  const size_t* n_elems, int dtype, double* const* d_d2, int accumulate,
+                                  void* stream) {
+  g_err.clear();
+  if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
+  if (b == 0) return DLSIM_OK;
+  if (!fan_in || !n_tensors || !d_d2) return fail(DLSIM_E_ARG, "null array argument");
+  const int rc = check_pairdist_tasks(b, fan_in, n_tensors, d_inputs, n_elems, d_d2, DLSIM_MAX_PAIRDIST_INPUTS, dtype,
+                                      accumulate, kPairdistLimit);
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = pairdist_batched(b, fan_in, n_tensors, d_inputs, n_elems, dtype, d_d2, accumulate,
+                                        static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "pairwise distance launch");
+}
+
+int dlsim_pairdist_batch_geometry(int n, int dtype, int* max_segments, int* max_ptrs) {
+  g_err.clear();
+  const int rc = check_fan_in(n, DLSIM_MAX_PAIRDIST_INPUTS, dtype, kPairdistLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!max_segments || !max_ptrs) return fail(DLSIM_E_ARG, "null result pointer");
+  *max_segments = DLSIM_PAIRDIST_BATCH_MAX_SEGMENTS;
+  *max_ptrs = DLSIM_PAIRDIST_BATCH_MAX_PTRS;
   return DLSIM_OK;
 }
 

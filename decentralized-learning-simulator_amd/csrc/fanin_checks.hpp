@@ -1,7 +1,10 @@
 // fanin_checks.hpp — the argument checks and the model-major gather that the
 // entries over n <= 32 inputs share (dlsim_robust_reduce, dlsim_pairwise_sqdist,
-// dlsim_wreduce_dist and their _tensors forms, dlsim_abi.hip). Host code only.
+// dlsim_wreduce_dist, their _tensors and _batched forms, dlsim_abi.hip). Host code only.
 #pragma once
+
+#include <algorithm>
+#include <vector>
 
 #include "abi_common.hpp"
 
@@ -74,6 +77,63 @@ inline int check_window_tasks(int b, const int* fan_in, const void* const* in, c
       if (rc != DLSIM_OK) return fail(rc, "task %d: %s", t, std::string(g_err).c_str());
     }
     off += static_cast<size_t>(n);
+  }
+  return DLSIM_OK;
+}
+
+// The task list of dlsim_pairwise_sqdist_batched: task k reads fan_in[k] * n_tensors[k] pointers,
+// model-major, and n_tensors[k] lengths at the running offsets, and writes fan_in[k]^2 doubles at
+// d2[k]. dtype and accumulate first; then per task, in order: 1 <= fan_in <= max, n_tensors >= 0, a
+// non-null matrix; then every non-empty tensor of every task (no null pointer) against every task's
+// matrix, and the matrices against each other: no byte shared.
+inline int check_pairdist_tasks(int b, const int* fan_in, const int* n_tensors, const void* const* in,
+                                const size_t* n_elems, double* const* d2, int max, int dtype, int accumulate,
+                                const char* reason) {
+  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  int rc = check_accumulate(accumulate);
+  if (rc != DLSIM_OK) return rc;
+  long long tensors = 0;
+  for (int k = 0; k < b; ++k) {
+    const int n = fan_in[k];
+    if (n < 1) return fail(DLSIM_E_ARG, "task %d: n must be >= 1 (got %d)", k, n);
+    if (n > max) return fail(DLSIM_E_ARG, "task %d: n must be <= %d (got %d): %s", k, max, n, reason);
+    if (n_tensors[k] < 0) return fail(DLSIM_E_ARG, "task %d: n_tensors must be >= 0 (got %d)", k, n_tensors[k]);
+    if (!d2[k]) return fail(DLSIM_E_ARG, "task %d: null distance matrix pointer", k);
+    tensors += n_tensors[k];
+  }
+  if (tensors > 0 && (!in || !n_elems)) return fail(DLSIM_E_ARG, "null array argument");
+  struct Mat {
+    uintptr_t a, b;
+    int task;
+  };
+  std::vector<Mat> mats(static_cast<size_t>(b));
+  for (int k = 0; k < b; ++k) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d2[k]);
+    mats[static_cast<size_t>(k)] = {a, a + sizeof(double) * static_cast<size_t>(fan_in[k]) * fan_in[k], k};
+  }
+  std::sort(mats.begin(), mats.end(), [](const Mat& x, const Mat& y) { return x.a < y.a; });
+  for (size_t k = 1; k < mats.size(); ++k)
+    if (mats[k].a < mats[k - 1].b)  // sorted by start and disjoint so far: the ends are sorted too
+      return fail(DLSIM_E_ARG, "the distance matrices of tasks %d and %d overlap", mats[k - 1].task, mats[k].task);
+  const size_t esz = elem_bytes(dtype);
+  size_t po = 0, lo = 0;
+  for (int k = 0; k < b; ++k) {
+    const int n = fan_in[k], t = n_tensors[k];
+    for (int j = 0; j < t; ++j) {
+      const size_t bytes = n_elems[lo + j] * esz;
+      if (bytes == 0) continue;  // never read: any pointer will do
+      for (int i = 0; i < n; ++i) {
+        const void* p = in[po + static_cast<size_t>(i) * t + j];
+        if (!p) return fail(DLSIM_E_ARG, "task %d, tensor %d: null input pointer at index %d", k, j, i);
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
+        auto it = std::upper_bound(mats.begin(), mats.end(), a0, [](uintptr_t v, const Mat& x) { return v < x.b; });
+        if (it != mats.end() && it->a < a1)
+          return fail(DLSIM_E_ARG, "task %d, tensor %d: the distance matrix of task %d overlaps input %d", k, j,
+                      it->task, i);
+      }
+    }
+    po += static_cast<size_t>(n) * static_cast<size_t>(t);
+    lo += static_cast<size_t>(t);
   }
   return DLSIM_OK;
 }

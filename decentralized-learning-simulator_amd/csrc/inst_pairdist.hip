@@ -8,18 +8,7 @@
 
 namespace dlsim_host __attribute__((visibility("hidden"))) {
 
-namespace {
-
-struct PdGeom {
-  int cap;          // rows of a diagonal unit: 4 or 8
-  bool cross;       // n > 8: diagonal and cross units in one launch
-  unsigned units;   // second grid dimension
-  unsigned active;  // units that hold at least one pair
-  size_t tile;      // elements a block takes per step
-  unsigned blocks;  // first grid dimension
-};
-
-// elems16: elements of a 16-byte vector; vec: every base is 16-byte aligned
+// (PdGeom: partials.hpp)
 PdGeom pd_geometry(int n, int elems16, size_t nelem, bool vec) {
   PdGeom g;
   g.cap = n <= 4 ? 4 : dlsim::kPdGroup;
@@ -42,6 +31,8 @@ PdGeom pd_geometry(int n, int elems16, size_t nelem, bool vec) {
   g.blocks = static_cast<unsigned>(std::min(cap, std::max<size_t>(tiles, 1)));
   return g;
 }
+
+namespace {
 
 template <class Op, bool VEC>
 void pd_launch_main(const PdGeom& g, const dlsim::PdSlots& s, int n, size_t nelem, double* ws, hipStream_t st) {

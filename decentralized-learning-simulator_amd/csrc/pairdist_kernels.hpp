@@ -83,6 +83,7 @@ struct PdF16 {
 // unit indexes them with its wave-uniform first row).
 struct PdSlots {
   const void* p[kPdMaxInputs];
+  __device__ const void* ptr(int i) const { return p[i]; }
 };
 
 // What a lane holds of one row between the load and the arithmetic: a 16-byte
@@ -137,8 +138,9 @@ constexpr int pd_diag_slot(int ra, int i, int j) { return i * ra - i * (i + 1) /
 
 // One item per lane and row: all loads first, then element by element the
 // rows' values widened and one subtraction and one fma per pair.
-template <class Op, int RA, int RB, bool VEC, bool CHECK, int LDP>
-__device__ __forceinline__ void pd_tile(const PdSlots& s, int a0, int na, int b0, int nb, size_t idx, size_t count,
+// (S: where the row pointers are, PdSlots or a task of a batch, PdTaskArgs.)
+template <class Op, int RA, int RB, bool VEC, bool CHECK, int LDP, class S>
+__device__ __forceinline__ void pd_tile(const S& s, int a0, int na, int b0, int nb, size_t idx, size_t count,
                                         double (&acc)[pd_pairs<RA, RB>()]) {
   using Raw = PdRaw<Op, VEC>;
   constexpr int kRB = RB ? RB : 1;
@@ -146,12 +148,12 @@ __device__ __forceinline__ void pd_tile(const PdSlots& s, int a0, int na, int b0
 #pragma unroll
   for (int i = 0; i < RA; ++i) {
     ra[i] = Raw::zero();
-    if (i < na) ra[i] = pd_load<Op, VEC, CHECK, LDP>(s.p[a0 + i], idx, count);
+    if (i < na) ra[i] = pd_load<Op, VEC, CHECK, LDP>(s.ptr(a0 + i), idx, count);
   }
 #pragma unroll
   for (int j = 0; j < RB; ++j) {
     rb[j] = Raw::zero();
-    if (j < nb) rb[j] = pd_load<Op, VEC, CHECK, LDP>(s.p[b0 + j], idx, count);
+    if (j < nb) rb[j] = pd_load<Op, VEC, CHECK, LDP>(s.ptr(b0 + j), idx, count);
   }
 #pragma unroll
   for (int e = 0; e < Raw::EV; ++e) {
@@ -182,12 +184,12 @@ __device__ __forceinline__ void pd_tile(const PdSlots& s, int a0, int na, int b0
 
 // A block's end: per accumulator the 64 lanes of a wave (xor butterfly), the
 // four waves through LDS in wave order, one store of the block's partial to
-// ws[k * gridDim.x + blockIdx.x]. (Shared with reducedist_kernels.hpp.)
+// ws[k * nblk + b]: block b of nblk (gridDim.x / blockIdx.x of a flat launch,
+// a segment's own virtual grid in a batch). (Shared with reducedist_kernels.hpp.)
 template <int NP>
 __device__ __forceinline__ void pd_block_sum(const double (&acc)[NP], double* __restrict__ ws,
-                                             double (*red)[kPdSlots]) {
+                                             double (*red)[kPdSlots], size_t nblk, size_t b) {
   static_assert(NP <= kPdSlots, "a block's partials fit its slots");
-  const size_t nblk = gridDim.x, b = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
@@ -215,11 +217,12 @@ __device__ __forceinline__ double pd_finish_sum(const double* __restrict__ src, 
 
 // One unit of one block: rows a0 .. a0 + na (and b0 .. b0 + nb of a cross
 // unit) over this block's share of the items, then the block's partial sums
-// to ws[slot * gridDim.x + blockIdx.x]. Every block of a unit stores all its
-// slots, zeros where it had no tile. red: kBlock / 64 rows of kPdSlots.
-template <class Op, int RA, int RB, bool VEC, int LDP>
-__device__ __forceinline__ void pd_unit(const PdSlots& s, int a0, int na, int b0, int nb, size_t nelem,
-                                        double* __restrict__ ws, double (*red)[kPdSlots]) {
+// to ws[slot * nblk + b] (block b of the unit's nblk, as pd_block_sum). Every
+// block of a unit stores all its slots, zeros where it had no tile. red:
+// kBlock / 64 rows of kPdSlots.
+template <class Op, int RA, int RB, bool VEC, int LDP, class S>
+__device__ __forceinline__ void pd_unit(const S& s, int a0, int na, int b0, int nb, size_t nelem,
+                                        double* __restrict__ ws, double (*red)[kPdSlots], size_t nblk, size_t b) {
   constexpr int NP = pd_pairs<RA, RB>();
   constexpr int EV = PdRaw<Op, VEC>::EV;
   static_assert(NP <= kPdSlots, "a unit's partials fit its slots");
@@ -228,7 +231,6 @@ __device__ __forceinline__ void pd_unit(const PdSlots& s, int a0, int na, int b0
   for (int k = 0; k < NP; ++k) acc[k] = 0.0;
   const size_t items = nelem / EV;  // whole vectors, or elements
   const size_t full = items / kBlock;
-  const size_t nblk = gridDim.x, b = blockIdx.x;
   for (size_t t = b; t < full; t += nblk)
     pd_tile<Op, RA, RB, VEC, false, LDP>(s, a0, na, b0, nb, t * kBlock + threadIdx.x, items, acc);
   // the partial tile goes to the block next in the deal, the < E elements
@@ -239,31 +241,30 @@ __device__ __forceinline__ void pd_unit(const PdSlots& s, int a0, int na, int b0
     if (items * EV < nelem && b == nblk - 1)
       pd_tile<Op, RA, RB, false, true, 0>(s, a0, na, b0, nb, items * EV + threadIdx.x, nelem, acc);
   }
-  pd_block_sum<NP>(acc, ws, red);
+  pd_block_sum<NP>(acc, ws, red, nblk, b);
 }
 
-// grid (blocks, units). CROSS = false: the one diagonal unit of n <= CAP rows
+// Block b of the nblk blocks of unit u over n rows of nelem elements, ws the
+// call's partials. CROSS = false: the one diagonal unit of n <= CAP rows
 // (CAP 4 or 8). CROSS = true (CAP 8, n > 8): units 0 .. G-1 are the groups'
 // diagonal units, unit G + 2 * pair + half the 8 rows of group ga against
 // rows 8 gb + 4 half .. + 4 of group gb, the pairs ga < gb numbered row by
 // row. Units without a pair of rows return at once.
-template <class Op, int CAP, bool CROSS, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_pairdist(const PdSlots s, int n, size_t nelem, double* __restrict__ ws) {
-  static_assert(kBlock == 256, "four waves: the block-end sum names them");
-  __shared__ double red[kBlock / 64][kPdSlots];
+template <class Op, int CAP, bool CROSS, bool VEC, class S>
+__device__ __forceinline__ void pd_block(const S& s, int n, size_t nelem, double* __restrict__ ws, int u, size_t nblk,
+                                         size_t b, double (*red)[kPdSlots]) {
   // rows read by several units stay cacheable; a single unit streams
   constexpr int LDP = CROSS ? 0 : 1;
-  const int u = blockIdx.y;
-  double* const wsu = ws + static_cast<size_t>(u) * kPdSlots * gridDim.x;
+  double* const wsu = ws + static_cast<size_t>(u) * kPdSlots * nblk;
   if constexpr (!CROSS) {
-    pd_unit<Op, CAP, 0, VEC, LDP>(s, 0, n, 0, 0, nelem, wsu, red);
+    pd_unit<Op, CAP, 0, VEC, LDP>(s, 0, n, 0, 0, nelem, wsu, red, nblk, b);
   } else {
     const int groups = (n + kPdGroup - 1) / kPdGroup;
     if (u < groups) {
       const int a0 = u * kPdGroup;
       const int na = min(kPdGroup, n - a0);
       if (na < 2) return;
-      pd_unit<Op, kPdGroup, 0, VEC, LDP>(s, a0, na, 0, 0, nelem, wsu, red);
+      pd_unit<Op, kPdGroup, 0, VEC, LDP>(s, a0, na, 0, 0, nelem, wsu, red, nblk, b);
     } else {
       int pair = (u - groups) >> 1, ga = 0;
       const int half = (u - groups) & 1;
@@ -275,9 +276,56 @@ __global__ __launch_bounds__(kBlock) void k_pairdist(const PdSlots s, int n, siz
       const int b0 = gb * kPdGroup + half * kPdCross;
       const int nb = min(kPdCross, n - b0);
       if (nb < 1) return;
-      pd_unit<Op, kPdGroup, kPdCross, VEC, LDP>(s, ga * kPdGroup, kPdGroup, b0, nb, nelem, wsu, red);
+      pd_unit<Op, kPdGroup, kPdCross, VEC, LDP>(s, ga * kPdGroup, kPdGroup, b0, nb, nelem, wsu, red, nblk, b);
     }
   }
+}
+
+// grid (blocks, units): block blockIdx.x of unit blockIdx.y (pd_block)
+template <class Op, int CAP, bool CROSS, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_pairdist(const PdSlots s, int n, size_t nelem, double* __restrict__ ws) {
+  static_assert(kBlock == 256, "four waves: the block-end sum names them");
+  __shared__ double red[kBlock / 64][kPdSlots];
+  pd_block<Op, CAP, CROSS, VEC>(s, n, nelem, ws, static_cast<int>(blockIdx.y), gridDim.x, blockIdx.x, red);
+}
+
+// sum + held: how a finish kernel adds its sum to what the matrix holds, as one
+// instruction with the operands in this order. For numbers the order is
+// immaterial; a NaN plus a NaN of another sign or payload (a NaN input in one
+// tensor, Inf - Inf in the next) keeps the first operand's bits, and the
+// compiler may commute a plain `+` differently in two kernels. Written out so
+// that k_pairdist_finish and k_pairdist_batch_finish agree bit for bit. The
+// order is the one `*pij + v` compiled to in k_pairdist_finish before the
+// batched kernels came (the sum in src0, the loaded value in src1: the device
+// assembly lines are in profiles/krum_batch/finish_add_operands.md, DESIGN.md
+// §8n), so the flat entry's bits did not move for NaN payloads either.
+__device__ __forceinline__ double pd_add_held(double sum, double held) {
+  double r;
+  asm("v_add_f64 %0, %1, %2" : "=v"(r) : "v"(sum), "v"(held));
+  return r;
+}
+
+// Pair number `pair` of n rows (i < j, numbered row by row) -> i, j and
+// unit * kPdSlots + slot: where the main kernel's units left the pair's
+// partials. cap: rows of the diagonal units (4 or 8).
+__device__ __forceinline__ int pd_pair_slot(int pair, int n, int cap, int& i, int& j) {
+  i = 0;
+  while (pair >= n - 1 - i) {
+    pair -= n - 1 - i;
+    ++i;
+  }
+  j = i + 1 + pair;
+  const int groups = (n + kPdGroup - 1) / kPdGroup;
+  const int gi = i / kPdGroup, gj = j / kPdGroup, li = i % kPdGroup, lj = j % kPdGroup;
+  int unit, slot;
+  if (gi == gj) {
+    unit = groups > 1 ? gi : 0;
+    slot = pd_diag_slot(cap, li, lj);
+  } else {
+    unit = groups + 2 * (gi * groups - gi * (gi + 1) / 2 + (gj - gi - 1)) + lj / kPdCross;
+    slot = li * kPdCross + lj % kPdCross;
+  }
+  return unit * kPdSlots + slot;
 }
 
 // One wave per pair i < j (numbered row by row): the pair's partials of all
@@ -292,29 +340,15 @@ __global__ __launch_bounds__(kBlock) void k_pairdist_finish(const double* __rest
   if (blockIdx.x == 0 && threadIdx.x < static_cast<unsigned>(n) && !accumulate)
     d2[static_cast<size_t>(threadIdx.x) * (n + 1)] = 0.0;
   const int lane = threadIdx.x & 63;
-  int pair = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const int pair = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (pair >= n * (n - 1) / 2) return;
-  int i = 0;
-  while (pair >= n - 1 - i) {
-    pair -= n - 1 - i;
-    ++i;
-  }
-  const int j = i + 1 + pair;
-  const int groups = (n + kPdGroup - 1) / kPdGroup;
-  const int gi = i / kPdGroup, gj = j / kPdGroup, li = i % kPdGroup, lj = j % kPdGroup;
-  int unit, slot;
-  if (gi == gj) {
-    unit = groups > 1 ? gi : 0;
-    slot = pd_diag_slot(cap, li, lj);
-  } else {
-    unit = groups + 2 * (gi * groups - gi * (gi + 1) / 2 + (gj - gi - 1)) + lj / kPdCross;
-    slot = li * kPdCross + lj % kPdCross;
-  }
-  const double* const src = ws + (static_cast<size_t>(unit) * kPdSlots + slot) * blocks;
+  int i, j;
+  const int where = pd_pair_slot(pair, n, cap, i, j);
+  const double* const src = ws + static_cast<size_t>(where) * blocks;
   const double v = pd_finish_sum(src, blocks, lane);
   if (lane == 0) {
     double* const pij = d2 + static_cast<size_t>(i) * n + j;
-    const double r = accumulate ? *pij + v : v;
+    const double r = accumulate ? pd_add_held(v, *pij) : v;
     *pij = r;
     d2[static_cast<size_t>(j) * n + i] = r;
   }

@@ -1,6 +1,8 @@
 // partials.hpp — what the host dispatches of the n <= 32 input families share (inst_robust.hip,
-// inst_pairdist.hip, inst_reducedist.hip): the split of a long input into launches of 32-bit byte
-// offsets, and the two distance families' grid cap, partial-sum workspace and finish grid. Host code only.
+// inst_pairdist.hip, inst_pairdist_batch.hip, inst_reducedist.hip): the split of a long input into
+// launches of 32-bit byte offsets, the distance families' grid cap, partial-sum workspace and finish
+// grid, and the grid of one pairwise-distance call (PdGeom), which the flat entry and every segment of
+// a batched launch take from the same pd_geometry. Host code only.
 #pragma once
 
 #include "dispatch.hpp"
@@ -35,6 +37,19 @@ hipError_t with_partials(size_t doubles, hipStream_t st, Body body) {
   const hipError_t e2 = hipFreeAsync(ws, st);
   return e == hipSuccess ? e2 : e;
 }
+
+// The grid of one pairwise-distance call (inst_pairdist.hip defines pd_geometry; a segment of a
+// batched launch takes the same one, inst_pairdist_batch.hip).
+struct PdGeom {
+  int cap;          // rows of a diagonal unit: 4 or 8
+  bool cross;       // n > 8: diagonal and cross units in one launch
+  unsigned units;   // second grid dimension
+  unsigned active;  // units that hold at least one pair
+  size_t tile;      // elements a block takes per step
+  unsigned blocks;  // first grid dimension
+};
+// elems16: elements of a 16-byte vector; vec: every base is 16-byte aligned
+PdGeom pd_geometry(int n, int elems16, size_t nelem, bool vec);
 
 inline unsigned finish_blocks(int items) {  // grid of a finish kernel: one wave per item (a pair, an input)
   return static_cast<unsigned>((items + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));

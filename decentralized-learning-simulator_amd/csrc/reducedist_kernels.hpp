@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_reducedist(const RdSlots<wt_t<typena
     if (items * EV < nelem && b == nblk - 1)
       rd_tile<Op, CAP, false, true>(s, n, out, items * EV + threadIdx.x, nelem, acc);
   }
-  pd_block_sum<CAP>(acc, ws, red);
+  pd_block_sum<CAP>(acc, ws, red, nblk, b);
 }
 
 // One wave per input: its partials of all blocks in pairdist's finish order.

@@ -69,6 +69,8 @@ EXPORTS = (
     "dlsim_pairwise_sqdist",
     "dlsim_pairwise_sqdist_tensors",
     "dlsim_pairdist_geometry",
+    "dlsim_pairwise_sqdist_batched",
+    "dlsim_pairdist_batch_geometry",
     "dlsim_wreduce_dist",
     "dlsim_wreduce_dist_tensors",
     "dlsim_reducedist_geometry",
@@ -220,6 +222,11 @@ def load() -> ctypes.CDLL:
         lib.dlsim_pairwise_sqdist_tensors.restype = i
         lib.dlsim_pairdist_geometry.argtypes = [i, i, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint)]
         lib.dlsim_pairdist_geometry.restype = i
+        lib.dlsim_pairwise_sqdist_batched.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(vp),
+                                                      ctypes.POINTER(sz), i, ctypes.POINTER(vp), i, vp]
+        lib.dlsim_pairwise_sqdist_batched.restype = i
+        lib.dlsim_pairdist_batch_geometry.argtypes = [i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
+        lib.dlsim_pairdist_batch_geometry.restype = i
         dp = ctypes.POINTER(ctypes.c_double)
         lib.dlsim_wreduce_dist.argtypes = [ctypes.POINTER(vp), i, dp, vp, sz, i, vp, i, vp]
         lib.dlsim_wreduce_dist.restype = i
@@ -683,6 +690,60 @@ def pairdist_geometry(n: int, torch_dtype, numel: int):
     """(tile elements, blocks) of dlsim_pairwise_sqdist for n 16-byte-aligned
     inputs of numel elements (dlsim_pairdist_geometry; no GPU needed)."""
     return _geometry("dlsim_pairdist_geometry", n, torch_dtype, numel)
+
+
+def pairwise_sqdist_batched_raw(fan_in: Sequence[int], n_tensors: Sequence[int], in_ptrs: Sequence[int],
+                                numels: Sequence[int], dtype: int, out_ptrs: Sequence[int], accumulate: bool,
+                                stream_handle) -> None:
+    """dlsim_pairwise_sqdist_batched on pointers the caller has already
+    validated: task k's fan_in[k] * n_tensors[k] pointers (model-major) and
+    n_tensors[k] lengths follow task k-1's; fan_in[k]^2 doubles at out_ptrs[k]."""
+    _check("dlsim_pairwise_sqdist_batched",
+           load().dlsim_pairwise_sqdist_batched(len(fan_in), _int_array(fan_in), _int_array(n_tensors),
+                                                _ptr_array(in_ptrs), _size_array(numels), dtype,
+                                                _ptr_array(out_ptrs), int(bool(accumulate)), stream_handle))
+
+
+def pairwise_sqdist_batched(tasks, accumulate: bool = False, stream=None):
+    """dlsim_pairwise_sqdist_batched: tasks = [(inputs, out)], each as
+    pairwise_sqdist takes them (its exceptions too), all of one dtype on one
+    device; every matrix in a few shared launches, bit-identical to one
+    pairwise_sqdist call each. No matrix may share memory with an input of any
+    task or with another matrix; inputs may be shared. Stream-ordered. Returns
+    the matrices."""
+    if not tasks:
+        return []
+    dev, dt0 = tasks[0][1].device, None
+    fan, ptrs, numels, outs = [], [], [], []
+    for inputs, out in tasks:
+        n = len(inputs)
+        if n < 1:
+            raise IndexError("list index out of range")
+        check_pairdist_fan_in(n)
+        _check_distances(out, n * n, "matrix")
+        dt, numel = _check_flat_inputs(inputs, None, dev, "pairwise distance")
+        if out.device != dev:
+            raise ValueError("the pairwise distance needs device tensors on one device (no CPU path)")
+        if dt0 is not None and dt != dt0:
+            raise ValueError("one batched call takes tasks of one dtype")
+        dt0 = dt
+        fan.append(n)
+        ptrs += [t.data_ptr() for t in inputs]
+        numels.append(numel)
+        outs.append(out.data_ptr())
+    pairwise_sqdist_batched_raw(fan, [1] * len(fan), ptrs, numels, dtype_code(dt0, single_task=True), outs,
+                                accumulate, _stream_handle(dev, stream))
+    return [t[1] for t in tasks]
+
+
+def pairdist_batch_geometry(n: int, torch_dtype):
+    """(max_segments, max_ptrs) of dlsim_pairdist_batch_geometry: the limits
+    of one launch of the batched distance kernel (no GPU needed)."""
+    ms, mp = ctypes.c_int(0), ctypes.c_int(0)
+    _check("dlsim_pairdist_batch_geometry",
+           load().dlsim_pairdist_batch_geometry(int(n), dtype_code(torch_dtype, single_task=True), ctypes.byref(ms),
+                                                ctypes.byref(mp)))
+    return ms.value, mp.value
 
 
 def wreduce_dist(inputs, weights: Sequence[float], out, d2, accumulate: bool = False, stream=None):

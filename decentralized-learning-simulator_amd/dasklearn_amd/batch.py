@@ -71,27 +71,66 @@ def method_plugin(method, settings):
     return ModelManager(None, _Settings(), 0).get_aggregation_method()
 
 
+def krum_rule(plugin):
+    """(name, f, m) when `plugin` is a Krum or MultiKrum class (a subclass
+    too: with_params makes one), else None. m: None for Krum, for Multi-Krum
+    the class's m or, by default, the function fan-in -> n - f."""
+    from .gradient_aggregation.krum import Krum, MultiKrum
+    if not isinstance(plugin, type):
+        return None
+    if issubclass(plugin, Krum):
+        return "Krum", plugin.f, None
+    if issubclass(plugin, MultiKrum):
+        f = plugin.f
+        return "MultiKrum", f, (lambda n: n - f) if plugin.m is None else plugin.m
+    return None
+
+
+def check_krum_task(rule, models, weights) -> None:
+    """What Krum / MultiKrum raise for one task before they touch the models,
+    in their order: AssertionError or ValueError for weights, IndexError for
+    no model, ValueError for more than 32 or for (n, f, m) outside the rule."""
+    from .gradient_aggregation.krum import check_krum_params
+    from .gradient_aggregation.robust import _check_unweighted
+    name, f, m = rule
+    _check_unweighted(name, models, weights)
+    models[0]
+    n = len(models)
+    _native.check_pairdist_fan_in(n)
+    check_krum_params(n, f, 1 if m is None else m(n) if callable(m) else m)
+
+
 def _aggregate_batch_method(tasks, method, settings) -> List[nn.Module]:
     """aggregate_batch for a method other than FedAvg."""
-    from .model_inputs import robust_arena_tasks
+    from .model_inputs import krum_arena_tasks, robust_arena_tasks
     plugin = method_plugin(method, settings)
     window = method_window(method, settings)
-    if window is None:
-        # Krum, Multi-Krum, geometric median, centered clipping (and an unknown
-        # value, which fails as the per-task path fails): the plugin per task,
-        # the result kept on the device
+    rule = krum_rule(plugin) if window is None else None
+    if window is None and rule is None:
+        # geometric median, centered clipping (and an unknown value, which
+        # fails as the per-task path fails): the plugin per task, the result
+        # kept on the device
         return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in tasks]
     results: List[Optional[nn.Module]] = [None] * len(tasks)
     prepared, where = [], []
     for ti, (models, weights) in enumerate(tasks):
-        check_window_task(method, window, models, weights)
+        if rule is None:
+            check_window_task(method, window, models, weights)
+        else:
+            check_krum_task(rule, models, weights)
         layout, _, views = input_arenas(models)  # ZipMismatch is a ValueError
         if _device_views(views) is None:  # host models, separate tensors, several devices: the plugin stages them
-            results[ti] = plugin.aggregate(models, weights=None)
+            # (Krum and Multi-Krum keep such a result on the device, as they did task by task)
+            results[ti] = plugin.aggregate(models, weights=None) if rule is None else \
+                plugin.aggregate(models, weights=None, to_host=False)
             continue
         prepared.append((models[0], layout, views, None))
         where.append(ti)
-    for ti, out in zip(where, robust_arena_tasks(prepared, window)):
+    if rule is None:
+        outs = robust_arena_tasks(prepared, window)
+    else:
+        outs = krum_arena_tasks(prepared, rule[1], rule[2])
+    for ti, out in zip(where, outs):
         results[ti] = out
     return results
 
@@ -107,7 +146,9 @@ def aggregate_batch(tasks: Sequence[Tuple[List[nn.Module], Optional[Sequence[flo
 
     method: a GradientAggregationMethod (None: FEDAVG), with its parameters
     read from `settings` as ModelManager reads them. MEDIAN and TRIMMED_MEAN
-    batch their device-arena tasks through dlsim_robust_reduce_batched and
+    batch their device-arena tasks through dlsim_robust_reduce_batched, KRUM
+    and MULTI_KRUM theirs through dlsim_pairwise_sqdist_batched with one
+    synchronisation for all of them (model_inputs.krum_arena_tasks), and
     raise, per task, what their plugins raise; the other methods call their
     plugin per task and keep the result on the device. `mode` applies to
     FedAvg alone."""

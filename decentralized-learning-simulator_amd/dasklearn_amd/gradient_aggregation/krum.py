@@ -32,19 +32,76 @@ AssertionError (as FedAvg), one of the right length ValueError. An empty model
 list raises IndexError; more than 32 models, or a model whose parameter list
 differs from models[0]'s, ValueError.
 
-Cost: the selection needs the matrix on the host, so every aggregate pays one
-D2H copy of n*n doubles and one stream synchronisation between the distance
-kernel and the copy or reduce that follows. A device-side selection is not
-implemented.
+Cost: the selection needs the matrix on the host, so a single aggregate pays
+one D2H copy of n*n doubles and one stream synchronisation between the
+distance kernel and the copy or reduce that follows. The aggregates of one
+simulated round (`RoundExecutor`, `aggregate_batch`) share them: every task's
+matrix comes from batched launches (csrc/pairdist_batch_kernels.hpp, DESIGN.md
+§8n) into one device buffer, one D2H copy and one synchronisation per device
+serve the whole wave, and the copies or reduces that follow are batched too
+(`model_inputs.krum_arena_tasks`). `model_distances_batch` is that first phase
+on its own. A device-side selection is not implemented.
 """
 import math
 from typing import List, Optional, Sequence
 
+import torch
 from torch import nn
 
+from dasklearn_amd import _native
+from dasklearn_amd.arena import _target_device, input_arenas
 from dasklearn_amd.gradient_aggregation import GradientAggregation
 from dasklearn_amd.gradient_aggregation.robust import _check_unweighted
-from dasklearn_amd.model_inputs import krum_modules, model_distances  # noqa: F401  (model_distances: public here)
+from dasklearn_amd.model_inputs import (distances_arena_tasks, krum_modules,  # noqa: F401
+                                        model_distances)  # (model_distances: public here)
+
+
+def _resident_entry(models: List[nn.Module], device):
+    """`models` as an entry of distances_arena_tasks when every parameter is
+    on one CUDA device (`device`, when given) as an arena or as contiguous
+    separate tensors; None when something would have to be copied first."""
+    layout, all_params, views = input_arenas(models)  # ZipMismatch is a ValueError
+    dev = None
+    resolved = {}
+    for dt, idx in layout.groups.items():
+        vs = views[dt]
+        ts = list(vs) if vs is not None else [ps[k] for ps in all_params for k in idx]
+        if vs is None:
+            if not all(t.is_contiguous() for t in ts):
+                return None
+            vs = [None] * len(models)
+        for t in ts:
+            if not t.is_cuda or (dev is not None and t.device != dev):
+                return None
+            dev = t.device
+        resolved[dt] = vs
+    if dev is None or (device is not None and dev != _target_device((), device)):
+        return None
+    return (models[0], layout, resolved, None, all_params)
+
+
+def model_distances_batch(tasks: Sequence[List[nn.Module]], device=None) -> List[torch.Tensor]:
+    """model_distances for every list of models in `tasks` (the consensus
+    distance of every neighbourhood of a round) in one call: the matrices of
+    the device-resident tasks come from batched launches, one D2H copy and one
+    stream synchronisation per device (model_inputs.distances_arena_tasks);
+    a task with a host model, a model on another device or a non-contiguous
+    parameter goes through model_distances. Each matrix is bit-identical to
+    model_distances(models, device); the exceptions are its too."""
+    results: List[Optional[torch.Tensor]] = [None] * len(tasks)
+    prepared, where = [], []
+    for ti, models in enumerate(tasks):
+        models[0]  # IndexError for an empty list, as model_distances
+        _native.check_pairdist_fan_in(len(models))
+        entry = _resident_entry(models, device)
+        if entry is None:
+            results[ti] = model_distances(models, device)
+            continue
+        prepared.append(entry)
+        where.append(ti)
+    for ti, d2 in zip(where, distances_arena_tasks(prepared)):
+        results[ti] = d2
+    return results
 
 
 def check_krum_params(n: int, f: int, m: int = 1) -> None:

@@ -20,8 +20,8 @@ anything else (host models, other devices) is copied once into a fresh arena
 aggregate chain never crosses PCIe when the train function works on the
 device. Results are bit-identical to running the same tasks one by one with
 functions.aggregate under the same settings.gradient_aggregation: FedAvg, the
-median and the trimmed mean in batched launches, the other methods through
-their plugin task by task (RoundExecutor._aggregate_wave_method).
+median, the trimmed mean, Krum and Multi-Krum in batched launches, the other
+methods through their plugin task by task (RoundExecutor._aggregate_wave_method).
 """
 from __future__ import annotations
 
@@ -34,9 +34,10 @@ from torch import nn
 from . import _native
 from .arena import (ParamLayout, ZipMismatch, _target_device, aggregate_modules, aligned_empty, arena_empty, base_align,
                     layout_of, module_params, registered_arenas, row_stride)
-from .batch import _device_views, _resolve, aggregate_arena_tasks, check_window_task, method_window
+from .batch import (_device_views, _resolve, aggregate_arena_tasks, check_krum_task, check_window_task, krum_rule,
+                    method_window)
 from .gradient_aggregation import GradientAggregationMethod
-from .model_inputs import robust_arena_tasks
+from .model_inputs import krum_arena_tasks, robust_arena_tasks
 from .model_manager import ModelManager
 
 Task = Tuple[str, str, dict]  # (task_name, func_name, data with placeholders)
@@ -306,7 +307,11 @@ class RoundExecutor:
         does (one upload of the host models, arenas and separate device
         tensors read in place) and run every task in one batched call per
         dtype (model_inputs.robust_arena_tasks); each task raises what its
-        plugin raises. The other methods (and an unknown value, which fails
+        plugin raises. KRUM and MULTI_KRUM, when ModelManager's plugin is a
+        Krum or MultiKrum class, resolve the models the same way and run the
+        wave in two batched phases around one synchronisation
+        (model_inputs.krum_arena_tasks), f and m read from the class. The
+        other methods and any other plugin (and an unknown value, which fails
         as the per-task path fails) call the plugin per task on the resolved
         models and keep the result on the device."""
         resolved = []
@@ -314,11 +319,17 @@ class RoundExecutor:
             d = self._resolve(data)
             resolved.append((d["models"], d.get("weights")))
         window = method_window(method, self.settings)
+        rule = None
         if window is None:
             plugin = ModelManager(None, self.settings, 0).get_aggregation_method()
-            return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in resolved]
+            rule = krum_rule(plugin)
+            if rule is None:
+                return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in resolved]
         for models, weights in resolved:
-            check_window_task(method, window, models, weights)
+            if rule is None:
+                check_window_task(method, window, models, weights)
+            else:
+                check_krum_task(rule, models, weights)
         cache: dict = {}
         walked: dict = {}
         self._upload_host_models([m for models, _ in resolved for m in models], cache, walked)
@@ -336,6 +347,8 @@ class RoundExecutor:
         resolved.clear()
         cache.clear()
         walked.clear()
+        if rule is not None:
+            return krum_arena_tasks(prepared, rule[1], rule[2], on_launched)
         return robust_arena_tasks(prepared, window, on_launched)
 
     def run(self, tasks: Sequence[Task], seed: Optional[Dict[str, list]] = None) -> Dict[str, list]:

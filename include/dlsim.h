@@ -776,6 +776,60 @@ int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, con
 int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
 
 /*
+ * dlsim_pairwise_sqdist_batched: b independent dlsim_pairwise_sqdist_tensors
+ * tasks in a few launches (the Krum or Multi-Krum distance matrices, or the
+ * consensus distances, of one simulated round's peers). The
+ * distance counterpart of dlsim_robust_reduce_batched. (New: it replaces no
+ * reference code.)
+ *   fan_in     host array of b fan-ins, 1 <= fan_in[k] <= 32
+ *   n_tensors  host array of b tensor counts, >= 0
+ *   d_inputs   host array of sum(fan_in[k] * n_tensors[k]) device pointers:
+ *              task k's, model-major (tensor j of model i at i*n_tensors[k] + j),
+ *              follow task k-1's
+ *   n_elems    host array of sum(n_tensors) element counts: task k's follow
+ *              task k-1's
+ *   d_d2       host array of b device pointers; task k writes fan_in[k]^2
+ *              doubles, row-major
+ *   accumulate 0 or 1, for every task, as dlsim_pairwise_sqdist
+ * Task k's matrix holds the bits that
+ *   dlsim_pairwise_sqdist_tensors(inputs_k, fan_in[k], n_tensors[k], n_elems_k,
+ *                                 dtype, d_d2[k], accumulate, stream)
+ * gives, for all four dtypes and any alignment: every non-empty tensor is a
+ * segment with the grid, the tiles and the block partials of its own flat
+ * call, and a matrix's segments are added in tensor order. fan_in[k] == 1
+ * writes the single 0; a task without an element (n_tensors[k] == 0, or every
+ * length 0) writes zeros, or nothing when accumulating; b == 0 is a no-op.
+ * The tasks are regrouped by the kernel's class (fan-in up to 4, up to 8,
+ * above) and run in launches of at most DLSIM_PAIRDIST_BATCH_MAX_SEGMENTS
+ * segments and DLSIM_PAIRDIST_BATCH_MAX_PTRS row pointers, aligned and
+ * misaligned segments in launches of their own; a task with a tensor past one
+ * launch's byte limit (2 GiB - 1 MiB) runs as dlsim_pairwise_sqdist_tensors
+ * runs it, and so does a call with b == 1 (one large task alone measured 6 %
+ * slower behind the batch's descriptors; the bits are the same
+ * either way). One stream-ordered workspace (hipMallocAsync / hipFreeAsync on
+ * `stream`) holds the partials of the whole call.
+ * Inputs may alias each other within and across tasks (in a ring one model is
+ * a row of several tasks). A matrix may share no byte with an input of any
+ * task, nor with another task's matrix. Argument errors (DLSIM_E_ARG: a null
+ * array or pointer, b < 0, a fan-in outside 1..32, n_tensors < 0, accumulate
+ * not 0 or 1, the overlaps above; DLSIM_E_DTYPE) are decided for the whole
+ * list before the first launch and before any HIP call. Stream-ordered; no
+ * synchronisation.
+ */
+#define DLSIM_PAIRDIST_BATCH_MAX_SEGMENTS 32
+#define DLSIM_PAIRDIST_BATCH_MAX_PTRS 192
+int dlsim_pairwise_sqdist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* d_inputs,
+                                  const size_t* n_elems, int dtype, double* const* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_pairdist_batch_geometry: the limits of one launch of
+ * dlsim_pairwise_sqdist_batched for tasks of fan-in n and this dtype, for
+ * tests that aim past them (a segment's tile and grid are
+ * dlsim_pairdist_geometry's). Host only. (New: no reference counterpart.)
+ */
+int dlsim_pairdist_batch_geometry(int n, int dtype, int* max_segments, int* max_ptrs);
+
+/*
  * dlsim_wreduce_dist: "reduce and measure", the exact weighted reduce of n
  * flat buffers and, from the same pass over them, every input's squared L2
  * distance to the reduce's own output. The primitive under the geometric

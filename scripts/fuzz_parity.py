@@ -47,6 +47,12 @@ shapes, dtypes, alignments, weights and special values, for a time budget.
               capacity classes in one call), window, size (empty ones too) and
               alignment of every buffer, one dtype (all four) per call, vs the
               same restatement per task; then one model as separate tensors
+  krum_batch  dlsim_pairwise_sqdist_batched: 1..44 tasks of
+              random fan-in 1..32 (all three classes in one call), 0..14
+              tensors of random length (empty ones too) and alignment, rows
+              shared between tasks, one dtype (all four) per call, with and
+              without accumulate, vs dlsim_pairwise_sqdist_tensors per task on
+              the same buffers, bit for bit, every matrix in guard bands
 
 Prints one JSON line with the case counts and the first failures (if any).
 
@@ -569,6 +575,72 @@ def robust_batch_case(rng, dtype):
                     sizes=[t[3].numel() for t in tasks], tensors_n=n, tensors=sizes)
 
 
+def krum_batch_case(rng, dtype):
+    """dlsim_pairwise_sqdist_batched against the flat entries on the same
+    buffers, bit for bit: the tensors form per task, and every task's matrix
+    in a guarded buffer."""
+    dt = DT[dtype]
+    esz = eu.ESIZE[dtype]
+    pool = {}  # shared rows: (length, offset) -> tensors that several tasks read
+
+    def row(p, off):
+        if rng.random() < 0.3 and pool.get((p, off)):
+            rows = pool[(p, off)]
+            return rows[int(rng.integers(0, len(rows)))]
+        buf = torch.empty(p + off, dtype=dt, device="cuda")
+        buf[off:].copy_((torch.randn(p, device="cuda") * float(np.exp(rng.uniform(-3, 3)))).to(dt))
+        if p and rng.random() < 0.1:
+            buf[off + int(rng.integers(0, p))] = float(rng.choice([np.inf, -np.inf, np.nan, 0.0]))
+        pool.setdefault((p, off), []).append(buf[off:])
+        return buf[off:]
+    b = int(rng.choice([1, 2, 7, 33, int(rng.integers(1, 45))]))
+    accumulate = bool(rng.random() < 0.4)
+    fans, nts, ptrs, lens, keep, budget = [], [], [], [], [], 4_000_000
+    for _ in range(b):
+        n = int(rng.choice([1, 2, 4, 5, 8, 9, 16, 17, 32, int(rng.integers(1, 33))]))
+        t = int(rng.choice([0, 1, 1, 1, 2, 5, 14]))
+        sizes = []
+        for _ in range(t):
+            p = int(rng.choice([0, 1, 3, 8, 9, 255, 1024, 1025, 2049, 4099, 8193, 65537, 300_001]))
+            if n * p > budget:
+                p = 1025
+            budget -= n * p
+            sizes.append(p)
+        # a task's tensors share one misalignment per tensor position, or every row its own
+        offs = [[int(rng.choice([0, 0, 0, 1, 2, 4])) for _ in range(n)] if rng.random() < 0.2 else
+                [int(rng.choice([0, 0, 0, 1, 2, 4]))] * n for _ in range(t)]
+        rows = [[row(p, offs[k][i]) for k, p in enumerate(sizes)] for i in range(n)]
+        fans.append(n)
+        nts.append(t)
+        ptrs.append([x.data_ptr() for r in rows for x in r])
+        lens.append(sizes)
+        keep.append(rows)
+    code = _native.dtype_code(dt, single_task=True)
+    stream = torch.cuda.current_stream().cuda_stream
+    pre = [torch.rand(n * n, dtype=torch.float64, device="cuda") for n in fans]
+    guards = [eu.guarded(n * n * 8, "f64", "cuda") for n in fans]
+    exps = []
+    for n, t, ps, ls, p0 in zip(fans, nts, ptrs, lens, pre):
+        d2 = p0.clone()
+        _native.pairwise_sqdist_tensors_raw(ps, n, ls, code, d2.data_ptr(), accumulate, stream)
+        exps.append(d2.cpu().view(torch.int64))
+    if accumulate:
+        for g, p0 in zip(guards, pre):
+            g.view.copy_(p0)
+    _native.pairwise_sqdist_batched_raw(fans, nts, [p for ps in ptrs for p in ps], [s for ls in lens for s in ls], code,
+                                        [g.view.data_ptr() for g in guards], accumulate, stream)
+    torch.cuda.synchronize()
+    bad = [k for k, (g, e) in enumerate(zip(guards, exps)) if not torch.equal(g.view.cpu().view(torch.int64), e)]
+    case = dict(kind="krum_batch", dtype=dtype, tasks=b, fan_ins=fans, tensors=lens, accumulate=accumulate,
+                elem_bytes=esz)
+    if bad:
+        case["tasks_that_differ"] = bad[:8]
+    dirty = [(k, d) for k, g in enumerate(guards) for d in eu.check_guards(g, limit=4)]
+    if dirty:
+        case["guard_bytes_written"] = dirty[:8]
+    return not bad and not dirty, case
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
@@ -579,7 +651,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     counts = {"reduce": 0, "reduce_fast": 0, "tensors": 0, "batched": 0, "chunk_mean": 0, "modules": 0,
               "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0, "sgdm": 0,
-              "robust": 0, "robust_batch": 0}
+              "robust": 0, "robust_batch": 0, "krum_batch": 0}
     fails = []
     t_end = time.time() + a.seconds
     t_note = time.time() + 20
@@ -590,14 +662,15 @@ def main():
         dtype = str(rng.choice(["f32", "bf16", "f16", "f64"]))
         which = rng.choice(["reduce", "tensors", "batched", "chunk_mean", "modules", "reconstruct",
                             "host_reduce", "host_chunk", "executor", "cached", "sharded", "sgd", "sgdm", "robust",
-                            "robust_batch"],
-                           p=[0.085, 0.085, 0.085, 0.085, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.07, 0.07, 0.04, 0.04])
+                            "robust_batch", "krum_batch"],
+                           p=[0.085, 0.07, 0.07, 0.085, 0.09, 0.09, 0.09, 0.05, 0.05, 0.04, 0.03, 0.07, 0.07, 0.04, 0.04,
+                              0.03])
         if only:
             which = str(rng.choice(only))
         if which in ("sgd", "sgdm") and dtype == "f16":
             dtype = "f32"  # fp16 has no SGD-step kernel (torch's CPU ops run it)
         if dtype == "f64" and which not in ("reduce", "chunk_mean", "host_chunk", "sharded", "sgd", "sgdm", "robust",
-                                                 "robust_batch"):
+                                                 "robust_batch", "krum_batch"):
             dtype = "f32"  # fp64 reduces are the single-task entry (dlsim_wreduce_f64); chunk means take fp64
         try:
             if which == "reduce":
@@ -822,6 +895,9 @@ def main():
             elif which == "robust_batch":
                 ok, case = robust_batch_case(rng, dtype)
                 counts["robust_batch"] += 1
+            elif which == "krum_batch":
+                ok, case = krum_batch_case(rng, dtype)
+                counts["krum_batch"] += 1
             elif which == "host_chunk":
                 from dasklearn_amd.arena import _side_streams
                 cpu_threads = int(rng.choice([1, 2, 4, 8, 16]))
