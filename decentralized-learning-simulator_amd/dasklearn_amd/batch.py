@@ -8,16 +8,22 @@ per 8-way task) one launch per task is launch-bound; `aggregate_batch` runs
 the tasks that are ready together through `dlsim_wreduce_batched` (up to 32
 tasks / 192 inputs per launch). Results are bit-identical to calling
 FedAvg.aggregate on each task.
+
+`method_route` decides, for `aggregate_batch` here and for RoundExecutor, which
+batched launches a method's tasks take; the tasks travel as
+wave_tasks.ArenaTask records, run by wave_tasks.aggregate_arena_tasks (FedAvg)
+and model_inputs' robust_arena_tasks and krum_arena_tasks.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
-import torch
 from torch import nn
 
 from . import _native
-from .arena import ZipMismatch, aggregate_modules, arena_empty, input_arenas, module_from_arenas
+from .arena import ZipMismatch, aggregate_modules, input_arenas
+from .model_inputs import krum_arena_tasks, robust_arena_tasks
+from .wave_tasks import ArenaTask, _device_views, aggregate_arena_tasks
 
 
 def _resolve(models, weights) -> List[float]:
@@ -100,39 +106,66 @@ def check_krum_task(rule, models, weights) -> None:
     check_krum_params(n, f, 1 if m is None else m(n) if callable(m) else m)
 
 
-def _aggregate_batch_method(tasks, method, settings) -> List[nn.Module]:
-    """aggregate_batch for a method other than FedAvg."""
-    from .model_inputs import krum_arena_tasks, robust_arena_tasks
-    plugin = method_plugin(method, settings)
+FEDAVG, WINDOW, KRUM, PLUGIN = "fedavg", "window", "krum", "plugin"
+
+
+class MethodRoute:
+    """How a method's aggregate tasks run (method_route). kind: FEDAVG (the weighted reduce), WINDOW
+    (the order statistics; rule: the lo_hi_fn), KRUM (rule: krum_rule's tuple) or PLUGIN (no batched
+    form: the plugin per task). plugin: the method's plugin class (None for FedAvg), looked up when the
+    route is made for KRUM and PLUGIN, which it decides between, and on first use for WINDOW."""
+    __slots__ = ("kind", "method", "rule", "_plugin", "_lookup")
+
+    def __init__(self, kind, method=None, rule=None, plugin=None, lookup=None):
+        self.kind, self.method, self.rule, self._plugin, self._lookup = kind, method, rule, plugin, lookup
+
+    @property
+    def plugin(self):
+        if self._lookup is not None:
+            self._plugin, self._lookup = self._lookup(), None
+        return self._plugin
+
+    def check(self, models, weights) -> None:
+        """Raise what the method's plugin raises for one task before it touches the models
+        (check_window_task, check_krum_task). FedAvg's weights rule is _resolve, which the dispatchers
+        call for the weights it returns."""
+        if self.kind == WINDOW:
+            check_window_task(self.method, self.rule, models, weights)
+        elif self.kind == KRUM:
+            check_krum_task(self.rule, models, weights)
+
+    def run(self, prepared, on_launched=None, mode: int = _native.DLSIM_EXACT, launchers=None) -> List[nn.Module]:
+        """One module per ArenaTask of `prepared`, in the method's batched launches (`mode`: FedAvg's).
+        launchers: (aggregate_arena_tasks, robust_arena_tasks, krum_arena_tasks) as the dispatcher's own
+        module names them (default: this module's), so that a probe or a test that replaces one of them
+        in the dispatcher's module sees that dispatcher's launches."""
+        fedavg, window, krum = launchers or (aggregate_arena_tasks, robust_arena_tasks, krum_arena_tasks)
+        if self.kind == FEDAVG:
+            return fedavg(prepared, mode, on_launched)
+        if self.kind == WINDOW:
+            return window(prepared, self.rule, on_launched)
+        return krum(prepared, self.rule[1], self.rule[2], on_launched)
+
+    def per_task(self, tasks) -> List[nn.Module]:
+        """PLUGIN: geometric median, centered clipping, a foreign plugin (and an unknown value, which
+        fails as the per-task path fails): the plugin per (models, weights), the result kept on the device."""
+        return [self.plugin.aggregate(models, weights=weights, to_host=False) for models, weights in tasks]
+
+
+def method_route(method, settings, lookup=method_plugin) -> MethodRoute:
+    """The one decision both dispatchers (aggregate_batch, RoundExecutor) make: FedAvg (None too) takes
+    the FedAvg launches; else a method_window the order-statistic launches; else a Krum or MultiKrum
+    plugin class (krum_rule) the Krum launches; else the plugin runs per task. lookup(method,
+    settings): the plugin class, as the caller's per-task path finds it."""
+    from .gradient_aggregation import GradientAggregationMethod
+    if method is None or method == GradientAggregationMethod.FEDAVG:
+        return MethodRoute(FEDAVG)
     window = method_window(method, settings)
-    rule = krum_rule(plugin) if window is None else None
-    if window is None and rule is None:
-        # geometric median, centered clipping (and an unknown value, which
-        # fails as the per-task path fails): the plugin per task, the result
-        # kept on the device
-        return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in tasks]
-    results: List[Optional[nn.Module]] = [None] * len(tasks)
-    prepared, where = [], []
-    for ti, (models, weights) in enumerate(tasks):
-        if rule is None:
-            check_window_task(method, window, models, weights)
-        else:
-            check_krum_task(rule, models, weights)
-        layout, _, views = input_arenas(models)  # ZipMismatch is a ValueError
-        if _device_views(views) is None:  # host models, separate tensors, several devices: the plugin stages them
-            # (Krum and Multi-Krum keep such a result on the device, as they did task by task)
-            results[ti] = plugin.aggregate(models, weights=None) if rule is None else \
-                plugin.aggregate(models, weights=None, to_host=False)
-            continue
-        prepared.append((models[0], layout, views, None))
-        where.append(ti)
-    if rule is None:
-        outs = robust_arena_tasks(prepared, window)
-    else:
-        outs = krum_arena_tasks(prepared, rule[1], rule[2])
-    for ti, out in zip(where, outs):
-        results[ti] = out
-    return results
+    if window is not None:
+        return MethodRoute(WINDOW, method, window, lookup=lambda: lookup(method, settings))
+    plugin = lookup(method, settings)
+    rule = krum_rule(plugin)
+    return MethodRoute(PLUGIN if rule is None else KRUM, method, rule, plugin)
 
 
 def aggregate_batch(tasks: Sequence[Tuple[List[nn.Module], Optional[Sequence[float]]]],
@@ -145,149 +178,38 @@ def aggregate_batch(tasks: Sequence[Tuple[List[nn.Module], Optional[Sequence[flo
     FedAvg.aggregate (where models[0] lives).
 
     method: a GradientAggregationMethod (None: FEDAVG), with its parameters
-    read from `settings` as ModelManager reads them. MEDIAN and TRIMMED_MEAN
-    batch their device-arena tasks through dlsim_robust_reduce_batched, KRUM
-    and MULTI_KRUM theirs through dlsim_pairwise_sqdist_batched with one
-    synchronisation for all of them (model_inputs.krum_arena_tasks), and
-    raise, per task, what their plugins raise; the other methods call their
-    plugin per task and keep the result on the device. `mode` applies to
-    FedAvg alone."""
-    from .gradient_aggregation import GradientAggregationMethod
-    if method is not None and method != GradientAggregationMethod.FEDAVG:
-        return _aggregate_batch_method(tasks, method, settings)
+    read from `settings` as ModelManager reads them (method_route). MEDIAN and
+    TRIMMED_MEAN batch their device-arena tasks through
+    dlsim_robust_reduce_batched, KRUM and MULTI_KRUM theirs through
+    dlsim_pairwise_sqdist_batched with one synchronisation for all of them
+    (model_inputs.krum_arena_tasks), and raise, per task, what their plugins
+    raise; the other methods call their plugin per task and keep the result on
+    the device. `mode` applies to FedAvg alone."""
+    route = method_route(method, settings)
+    if route.kind == PLUGIN:
+        return route.per_task(tasks)
     results: List[Optional[nn.Module]] = [None] * len(tasks)
     prepared, where = [], []
     for ti, (models, weights) in enumerate(tasks):
-        ws = _resolve(models, weights)
-        model0 = models[0]  # IndexError for an empty task, as the reference
+        route.check(models, weights)
+        ws = _resolve(models, weights) if route.kind == FEDAVG else None
+        model0 = models[0]  # FedAvg: IndexError for an empty task, as the reference (the others: in check)
         try:
             layout, _, views = input_arenas(models)
-        except ZipMismatch:  # parameter lists differ: the per-parameter zip path
+        except ZipMismatch:  # parameter lists differ: FedAvg's per-parameter zip path; else the ValueError it is
+            if route.kind != FEDAVG:
+                raise
             layout, views = None, None
-        if _device_views(views) is None:
-            results[ti] = aggregate_modules(models, weights, mode)
+        if _device_views(views) is None:  # host models, separate tensors, several devices: staged per task
+            if route.kind == FEDAVG:
+                results[ti] = aggregate_modules(models, weights, mode)
+            elif route.kind == WINDOW:
+                results[ti] = route.plugin.aggregate(models, weights=None)
+            else:  # Krum and Multi-Krum keep such a result on the device, as they did task by task
+                results[ti] = route.plugin.aggregate(models, weights=None, to_host=False)
             continue
-        prepared.append((model0, layout, views, ws))
+        prepared.append(ArenaTask(model0, layout, views, ws))
         where.append(ti)
-    for ti, out in zip(where, aggregate_arena_tasks(prepared, mode)):
+    for ti, out in zip(where, route.run(prepared, None, mode)):
         results[ti] = out
     return results
-
-
-def _device_views(views) -> Optional[torch.device]:
-    """The one CUDA device every flat view lives on, or None."""
-    dev = None
-    if not views:
-        return None
-    for vs in views.values():
-        if vs is None:
-            return None
-        for v in vs:
-            if not v.is_cuda or (dev is not None and v.device != dev):
-                return None
-            dev = v.device
-    return dev
-
-
-def _row_on(params, view, idx, sizes, dev):
-    """Model i's tensors of a dtype group as the rows path reads them: its
-    parameters when they are on `dev` (read in place; a registered arena's
-    parameters are views of it), else the pieces of its flat view (an arena
-    uploaded or copied to `dev`, e.g. a host model of the wave)."""
-    if view is None or params[idx[0]].device == dev:
-        return params
-    row = [None] * len(params)
-    for k, piece in zip(idx, view.split(sizes)):
-        row[k] = piece
-    return row
-
-
-def _rows_device(vs, rows, layout, dt) -> torch.device:
-    """The task's device: that of its flat views, or (none) of the first
-    model read in place (its tensors are on the target device by
-    construction, RoundExecutor._arena_of)."""
-    for v in vs:
-        if v is not None:
-            return v.device
-    t = rows[0][layout.groups[dt][0]]
-    if not t.is_cuda:
-        raise ValueError("rows input: tensors must be on a CUDA device")
-    return t.device
-
-
-def aggregate_arena_tasks(prepared, mode: int = _native.DLSIM_EXACT,
-                          on_launched: Optional[Callable[[], None]] = None) -> List[nn.Module]:
-    """prepared: [(model0, layout of model0, {dtype: [flat arena per model]},
-    weights as Python floats[, rows])] with every arena on one device -> one
-    module per task (deepcopy(model0) semantics, parameters views of a fresh
-    output arena), all tasks of a dtype and device in batched launches (fp64
-    groups: one dlsim_wreduce_f64 per task).
-
-    rows (optional): every model's parameter list. A dtype group whose arena
-    list holds None (a model that keeps its parameters in separate device
-    tensors, e.g. a device train task's deepcopy) is read from those tensors
-    in place: every such task's tensors in one dlsim_wreduce_batched call per
-    dtype and device (one sub-task per tensor, pointers collected in C),
-    instead of copying each such model into an arena first.
-
-    on_launched: called once every launch is queued, before the output
-    modules are built; the list `prepared` is consumed while they are (each
-    entry set to None once its module exists). A caller that drops its own
-    references to the input modules there lets them go as the outputs are
-    made: the arenas stay alive through the launch views, and the stream
-    orders any reuse of their memory after the kernels."""
-    by_dtype = {}
-    by_rows = {}
-    outs = []
-    for entry in prepared:
-        model0, layout, views, ws = entry[:4]
-        o = {}
-        for dt, vs in views.items():
-            if any(v is None for v in vs):
-                rows = entry[4]
-                dev = _rows_device(vs, rows, layout, dt)
-                out = arena_empty(layout.totals[dt], dt, dev)
-                o[dt] = out
-                idx = layout.groups[dt]
-                rows = [_row_on(rows[i], v, idx, layout.split_sizes[dt], dev) for i, v in enumerate(vs)]
-                by_rows.setdefault((dt, dev), []).append(
-                    ((rows, idx, layout.split_sizes[dt], _native.weights_for_dtype(ws, dt), out.data_ptr(),
-                      layout.byte_offsets[dt]), vs, out))
-                continue
-            dev = vs[0].device
-            out = arena_empty(layout.totals[dt], dt, dev)
-            o[dt] = out
-            by_dtype.setdefault((dt, dev), []).append((vs, _native.weights_for_dtype(ws, dt), out))
-        outs.append(o)
-    for (dt, dev), group in by_rows.items():
-        # every task read from separate tensors: one library call for all
-        stream = torch.cuda.current_stream(dev)
-        code = _native.dtype_code(dt)
-        if _native.wreduce_rows_multi([g[0] for g in group], code, mode, stream.cuda_stream, dev.index):
-            continue
-        for (rows, idx, sizes, w, out_ptr, offs), vs, out in group:
-            if not _native.wreduce_rows(rows, idx, sizes, w, out_ptr, offs, code, mode, stream.cuda_stream, dev.index):
-                # a model's tensors are elsewhere (its arena was copied
-                # here): flatten the in-place ones too, one reduce
-                with torch.no_grad():
-                    flat = [v if v is not None else
-                            torch._C._nn.flatten_dense_tensors([rows[i][k] for k in idx]).to(dev)
-                            for i, v in enumerate(vs)]
-                _native.wreduce(flat, w, out, mode, stream)
-    by_rows.clear()
-    for (dt, dev), group in by_dtype.items():
-        stream = torch.cuda.current_stream(dev)
-        if dt == torch.float64:
-            for vs, w, out in group:
-                _native.wreduce(vs, w, out, mode, stream)
-            continue
-        _native.wreduce_batched(group, mode, stream)
-    by_dtype.clear()
-    if on_launched is not None:
-        on_launched()
-    mods = []
-    for i, o in enumerate(outs):
-        model0, layout = prepared[i][:2]
-        prepared[i] = None
-        mods.append(module_from_arenas(model0, layout, o))
-    return mods

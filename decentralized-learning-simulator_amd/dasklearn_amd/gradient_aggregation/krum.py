@@ -54,10 +54,11 @@ from dasklearn_amd.gradient_aggregation import GradientAggregation
 from dasklearn_amd.gradient_aggregation.robust import _check_unweighted
 from dasklearn_amd.model_inputs import (distances_arena_tasks, krum_modules,  # noqa: F401
                                         model_distances)  # (model_distances: public here)
+from dasklearn_amd.wave_tasks import ArenaTask
 
 
-def _resident_entry(models: List[nn.Module], device):
-    """`models` as an entry of distances_arena_tasks when every parameter is
+def _resident_entry(models: List[nn.Module], device) -> Optional[ArenaTask]:
+    """`models` as a task of distances_arena_tasks when every parameter is
     on one CUDA device (`device`, when given) as an arena or as contiguous
     separate tensors; None when something would have to be copied first."""
     layout, all_params, views = input_arenas(models)  # ZipMismatch is a ValueError
@@ -77,7 +78,7 @@ def _resident_entry(models: List[nn.Module], device):
         resolved[dt] = vs
     if dev is None or (device is not None and dev != _target_device((), device)):
         return None
-    return (models[0], layout, resolved, None, all_params)
+    return ArenaTask(models[0], layout, resolved, None, all_params)
 
 
 def model_distances_batch(tasks: Sequence[List[nn.Module]], device=None) -> List[torch.Tensor]:

@@ -1,6 +1,8 @@
 """The aggregates over n <= 32 models (median and trimmed mean; pairwise distances and Krum; the
 reduce-and-measure pass of the geometric median and centered clipping) and ModelInputs, which resolves
-a list of models into what their kernels read. arena.py re-exports the public names."""
+a list of models into what their kernels read. arena.py re-exports the public names. The batched forms
+(robust_arena_tasks, distances_arena_tasks, krum_arena_tasks) take lists of wave_tasks.ArenaTask, whose
+module describes the record; batch.method_route picks among them."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -13,6 +15,7 @@ from . import _native
 from .arena import (ParamLayout, _arena_entry, _clone_module, _data_ptrs, _elem_size, _register_arenas, _restride,
                     _target_device, aggregate_modules, aligned_empty, arena_empty, arenas_to_host, base_align,
                     input_arenas, module_from_arenas, module_params, row_stride)
+from .wave_tasks import ArenaTask, aggregate_arena_tasks, finish_modules, output_arenas
 
 
 def _stage_rows(all_params, idx, total: int, dt: torch.dtype, dev: torch.device):
@@ -139,74 +142,47 @@ def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Opti
     return inputs.module(outs, to_host)
 
 
-def robust_arena_tasks(prepared, lo_hi_fn, on_launched=None) -> List[nn.Module]:
-    """batch.aggregate_arena_tasks for the coordinate-wise order statistics:
-    the same `prepared` entries, (model0, layout of model0, {dtype: [flat arena
-    per model]}, weights (unused: these aggregates are unweighted)[, rows]),
-    every task's window [lo, hi) = lo_hi_fn(its fan-in), one
-    dlsim_robust_reduce_batched call per dtype and device over all tasks. A
-    dtype group whose arena list holds None is read from the models' separate
-    tensors in place (`rows`), one sub-task per tensor of the same call.
-    on_launched and the consumption of `prepared`: as aggregate_arena_tasks.
-    More than 32 models in a task raise ValueError before anything is queued."""
-    from .batch import _row_on, _rows_device
+def robust_arena_tasks(prepared: List[ArenaTask], lo_hi_fn, on_launched=None) -> List[nn.Module]:
+    """wave_tasks.aggregate_arena_tasks for the coordinate-wise order statistics
+    (the weights are not read: these aggregates are unweighted): every task's
+    window [lo, hi) = lo_hi_fn(its fan-in), one dlsim_robust_reduce_batched
+    call per dtype and device over all tasks, a group read in place one
+    sub-task per tensor of the same call. on_launched and the consumption of
+    `prepared`: wave_tasks.finish_modules. More than 32 models in a task raise
+    ValueError before anything is queued."""
     calls: Dict[tuple, list] = {}  # (dtype, device) -> [fan-ins, pointers, los, his, out pointers, lengths, keep]
     outs = []
-    for entry in prepared:
-        model0, layout, views = entry[:3]
-        o = {}
-        for dt, vs in views.items():
-            n = len(vs)
+    for task in prepared:
+        if task.views:
+            n = task.fan_in
             _native.check_robust_fan_in(n)
             lo, hi = lo_hi_fn(n)
-            total = layout.totals[dt]
-            in_place = any(v is None for v in vs)
-            dev = _rows_device(vs, entry[4], layout, dt) if in_place else vs[0].device
-            out = o[dt] = arena_empty(total, dt, dev)
+        for dt, total, vs, in_place, dev, out in output_arenas(task, outs):
             if total == 0:
                 continue
             c = calls.setdefault((dt, dev), [[], [], [], [], [], [], []])
-            if not in_place:
-                c[0].append(n)
-                c[1] += [v.data_ptr() for v in vs]
-                c[2].append(lo)
-                c[3].append(hi)
-                c[4].append(out.data_ptr())
-                c[5].append(total)
+            if in_place:  # one sub-task per non-empty tensor
+                rows, live = task.tensor_rows(dt, vs, dev)
+                base, esz, offsets = out.data_ptr(), out.element_size(), task.layout.offsets
+                subs = [([r[k].data_ptr() for r in rows], base + offsets[k] * esz, size) for k, size in live]
+                c[6].append(rows)
+            else:
+                subs = [([v.data_ptr() for v in vs], out.data_ptr(), total)]
                 c[6].append(vs)
-                continue
-            idx, sizes, base = layout.groups[dt], layout.split_sizes[dt], out.data_ptr()
-            rows = [_row_on(entry[4][i], v, idx, sizes, dev) for i, v in enumerate(vs)]
-            for k, size, off in zip(idx, sizes, layout.byte_offsets[dt]):
-                if size == 0:
-                    continue
-                ts = [r[k] for r in rows]
-                for t in ts:
-                    if t.device != dev or t.dtype != dt or t.numel() != size or not t.is_contiguous():
-                        raise ValueError("rows input: tensors must be contiguous, of the layout's dtype and size, "
-                                         "on the task's device")
+            for ptrs, out_ptr, size in subs:
                 c[0].append(n)
-                c[1] += [t.data_ptr() for t in ts]
+                c[1] += ptrs
                 c[2].append(lo)
                 c[3].append(hi)
-                c[4].append(base + off)
+                c[4].append(out_ptr)
                 c[5].append(size)
-            c[6].append(rows)
-        outs.append(o)
     with torch.no_grad():
         for (dt, dev), (fan, ptrs, los, his, out_ptrs, numels, _) in calls.items():
             _native.robust_reduce_batched_raw(fan, ptrs, los, his, out_ptrs, numels,
                                               _native.dtype_code(dt, single_task=True),
                                               torch._C._cuda_getCurrentRawStream(dev.index))
     calls.clear()
-    if on_launched is not None:
-        on_launched()
-    mods = []
-    for i, o in enumerate(outs):
-        model0, layout = prepared[i][:2]
-        prepared[i] = None
-        mods.append(module_from_arenas(model0, layout, o))
-    return mods
+    return finish_modules(prepared, outs, on_launched)
 
 
 def _distances(inputs: ModelInputs) -> torch.Tensor:
@@ -241,78 +217,38 @@ def model_distances(models: List[nn.Module], device=None) -> torch.Tensor:
     return _distances(ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance", device))
 
 
-def _rows_tensors(entry, layout, dt, vs, dev):
-    """The models' tensors of a dtype group that is read in place from
-    separate tensors (robust_arena_tasks' rule): (rows, indices and sizes of
-    the group's non-empty tensors), every tensor checked against the layout."""
-    from .batch import _row_on
-    idx, sizes = layout.groups[dt], layout.split_sizes[dt]
-    rows = [_row_on(entry[4][i], v, idx, sizes, dev) for i, v in enumerate(vs)]
-    live = [(k, size) for k, size in zip(idx, sizes) if size]
-    for r in rows:
-        for k, size in live:
-            t = r[k]
-            if t.device != dev or t.dtype != dt or t.numel() != size or not t.is_contiguous():
-                raise ValueError("rows input: tensors must be contiguous, of the layout's dtype and size, "
-                                 "on the task's device")
-    return rows, live
-
-
-def _entry_fan_in(entry) -> int:
-    """The number of models of a `prepared` entry: the length of a dtype
-    group's view list, or of `rows` when the models have no parameters (and so
-    no group). Without either the entry does not say: ValueError."""
-    for vs in entry[2].values():
-        return len(vs)
-    if len(entry) < 5:
-        raise ValueError("a task without parameters and without rows does not state its fan-in")
-    return len(entry[4])
-
-
-def distances_arena_tasks(prepared) -> List[torch.Tensor]:
+def distances_arena_tasks(prepared: List[ArenaTask]) -> List[torch.Tensor]:
     """model_distances for many tasks at once: one host [n, n] float64 matrix
-    per entry of `prepared` (batch.aggregate_arena_tasks' form; the weights
-    are not read), bit-identical to model_distances on the same models. All
-    matrices of a device live in one device buffer and come back with one D2H
-    copy, which waits for the stream: one synchronisation per device, not one
-    per task. Each device's calls are issued with that device current (the
-    library allocates its workspace on the current device).
+    per task of `prepared` (the weights are not read), bit-identical to
+    model_distances on the same models. All matrices of a device live in one
+    device buffer and come back with one D2H copy, which waits for the stream:
+    one synchronisation per device, not one per task. Each device's calls are
+    issued with that device current (the library allocates its workspace on
+    the current device).
 
     A dtype group with arena views is one segment of
-    dlsim_pairwise_sqdist_batched, a group read in place from separate tensors
-    (`None` views and `rows`) one segment per non-empty tensor. A model's
-    dtype groups add into its matrix in its own layout order: the calls go in
-    rounds, round r takes every task's r-th non-empty group, one call per
-    (dtype, device) inside a round, accumulating from round 1 on. `prepared`
-    is only read. More than 32 models in a task raise ValueError before
-    anything is queued. Models without parameters give n x n zeros, as
-    model_distances does, with n read from `rows`."""
-    from .batch import _rows_device
+    dlsim_pairwise_sqdist_batched, a group read in place one segment per
+    non-empty tensor. A model's dtype groups add into its matrix in its own
+    layout order: the calls go in rounds, round r takes every task's r-th
+    non-empty group, one call per (dtype, device) inside a round, accumulating
+    from round 1 on. `prepared` is only read. More than 32 models in a task
+    raise ValueError before anything is queued. Models without parameters give
+    n x n zeros, as model_distances does, with n read from `rows`."""
     plans = []  # per task: (fan-in, device or None, [(dtype, n_tensors, pointers, lengths)])
     keep = []
     sizes: Dict[torch.device, int] = {}
-    for entry in prepared:
-        layout, views = entry[1], entry[2]
-        n, dev, groups = None, None, []
-        for dt in layout.groups:
-            vs = views[dt]
-            n = len(vs)
-            _native.check_pairdist_fan_in(n)
-            total = layout.totals[dt]
-            if total == 0:
-                continue
-            if not any(v is None for v in vs):
-                dev = vs[0].device
+    for task in prepared:
+        n = task.fan_in
+        _native.check_pairdist_fan_in(n)
+        dev, groups = None, []
+        for dt, total, vs, in_place, dev in task.groups(empty=False):
+            if not in_place:
                 groups.append((dt, 1, [v.data_ptr() for v in vs], [total]))
                 keep.append(vs)
                 continue
-            dev = _rows_device(vs, entry[4], layout, dt)
-            rows, live = _rows_tensors(entry, layout, dt, vs, dev)
+            rows, live = task.tensor_rows(dt, vs, dev)
             groups.append((dt, len(live), [r[k].data_ptr() for r in rows for k, _ in live], [s for _, s in live]))
             keep.append(rows)
-        if n is None:  # models without parameters: n x n zeros, as model_distances
-            n = _entry_fan_in(entry)
-            _native.check_pairdist_fan_in(n)
         off = None
         if dev is not None:
             off = sizes.get(dev, 0)
@@ -346,31 +282,30 @@ def distances_arena_tasks(prepared) -> List[torch.Tensor]:
             for n, dev, off, _ in plans]
 
 
-def krum_arena_tasks(prepared, f: int, m, on_launched=None) -> List[nn.Module]:
-    """batch.aggregate_arena_tasks for Krum (m None) and Multi-Krum (m an int,
-    or a callable fan-in -> m) with Byzantine count f: the same `prepared`
-    entries (the weights unused: these aggregates are unweighted), each task
-    what krum_modules gives for its models, bit for bit. Two phases around
-    one synchronisation per device: every task's distance matrix in batched
-    launches and one D2H copy (distances_arena_tasks), the selection per task
-    on the host (krum.krum_select), then
+def krum_arena_tasks(prepared: List[ArenaTask], f: int, m, on_launched=None) -> List[nn.Module]:
+    """wave_tasks.aggregate_arena_tasks for Krum (m None) and Multi-Krum (m an
+    int, or a callable fan-in -> m) with Byzantine count f (the weights are not
+    read: these aggregates are unweighted), each task what krum_modules gives
+    for its models, bit for bit. Two phases around one synchronisation per
+    device: every task's distance matrix in batched launches and one D2H copy
+    (distances_arena_tasks), the selection per task on the host
+    (krum.krum_select), then
       Krum:       the selected models' values copied bit for bit into fresh
                   output arenas, all tasks in one torch._foreach_copy_ per
                   device;
-      Multi-Krum: one aggregate_arena_tasks call over all tasks, each with
-                  model0 and the layout of its models[0], the selected models'
-                  views and rows in ascending index order and float(1./m) each
-                  in DLSIM_EXACT, as FedAvg.aggregate(selected).
+      Multi-Krum: one aggregate_arena_tasks call over all tasks, each the
+                  selected models in ascending index order (ArenaTask.select)
+                  with float(1./m) each in DLSIM_EXACT, as
+                  FedAvg.aggregate(selected).
     Buffers, attributes and strides are models[0]'s. on_launched fires once
     the second phase is queued (the inputs are read after the synchronisation,
     so they must live until then); `prepared` is consumed as in
     aggregate_arena_tasks. More than 32 models or (n, f, m) outside Krum's
     rule raise ValueError before anything is queued."""
     from dasklearn_amd.gradient_aggregation import krum as _krum
-    from .batch import _rows_device, aggregate_arena_tasks
     ms = []
-    for entry in prepared:
-        n = _entry_fan_in(entry)
+    for task in prepared:
+        n = task.fan_in
         _native.check_pairdist_fan_in(n)
         mk = 1 if m is None else int(m(n)) if callable(m) else int(m)
         _krum.check_krum_params(n, f, mk)
@@ -378,25 +313,16 @@ def krum_arena_tasks(prepared, f: int, m, on_launched=None) -> List[nn.Module]:
     chosen = [_krum.krum_select(d.tolist(), f, mk) for d, mk in zip(distances_arena_tasks(prepared), ms)]
     if m is not None:
         selected = []
-        for i, (entry, idx, mk) in enumerate(zip(prepared, chosen, ms)):
-            model0, layout, views = entry[:3]
-            e = (model0, layout, {dt: [vs[j] for j in idx] for dt, vs in views.items()}, [float(1. / mk)] * mk)
-            selected.append(e + ([entry[4][j] for j in idx],) if len(entry) > 4 else e)
+        for i, (task, idx, mk) in enumerate(zip(prepared, chosen, ms)):
+            selected.append(task.select(idx, [float(1. / mk)] * mk))
             prepared[i] = None
-        layouts = [e[1] for e in selected]
+        layouts = [t.layout for t in selected]
         mods = aggregate_arena_tasks(selected, _native.DLSIM_EXACT, on_launched)
         return [_restride(mod, layout) for mod, layout in zip(mods, layouts)]
     outs = []
     copies: Dict[torch.device, tuple] = {}
-    for entry, (w,) in zip(prepared, chosen):
-        layout, views = entry[1], entry[2]
-        o = {}
-        for dt, idx in layout.groups.items():
-            vs = views[dt]
-            total = layout.totals[dt]
-            in_place = any(v is None for v in vs)
-            dev = _rows_device(vs, entry[4], layout, dt) if in_place else vs[0].device
-            out = o[dt] = arena_empty(total, dt, dev)
+    for task, (w,) in zip(prepared, chosen):
+        for dt, total, vs, in_place, dev, out in output_arenas(task, outs):
             if total == 0:
                 continue
             dst, src = copies.setdefault(dev, ([], []))
@@ -404,26 +330,17 @@ def krum_arena_tasks(prepared, f: int, m, on_launched=None) -> List[nn.Module]:
                 dst.append(out)
                 src.append(vs[w])
                 continue
-            params = entry[4][w]  # read in place; distances_arena_tasks checked every row against the layout
-            for k, size in zip(idx, layout.split_sizes[dt]):
-                if size:
-                    off = layout.offsets[k]
-                    dst.append(out[off:off + size])
-                    src.append(params[k].detach().reshape(-1))
-        outs.append(o)
+            (params,), live = task.tensor_rows(dt, vs, dev, (w,))  # read in place
+            for k, size in live:
+                off = task.layout.offsets[k]
+                dst.append(out[off:off + size])
+                src.append(params[k].detach().reshape(-1))
     with torch.no_grad():
         for dev, (dst, src) in copies.items():
             with torch.cuda.device(dev):
                 torch._foreach_copy_(dst, src)
     copies.clear()
-    if on_launched is not None:
-        on_launched()
-    mods = []
-    for i, o in enumerate(outs):
-        model0, layout = prepared[i][:2]
-        prepared[i] = None
-        mods.append(_restride(module_from_arenas(model0, layout, o), layout))
-    return mods
+    return finish_modules(prepared, outs, on_launched, restride=True)
 
 
 class ReduceDistPlan:

@@ -21,7 +21,8 @@ aggregate chain never crosses PCIe when the train function works on the
 device. Results are bit-identical to running the same tasks one by one with
 functions.aggregate under the same settings.gradient_aggregation: FedAvg, the
 median, the trimmed mean, Krum and Multi-Krum in batched launches, the other
-methods through their plugin task by task (RoundExecutor._aggregate_wave_method).
+methods through their plugin task by task (batch.method_route decides; a
+task travels as a wave_tasks.ArenaTask).
 """
 from __future__ import annotations
 
@@ -34,11 +35,11 @@ from torch import nn
 from . import _native
 from .arena import (ParamLayout, ZipMismatch, _target_device, aggregate_modules, aligned_empty, arena_empty, base_align,
                     layout_of, module_params, registered_arenas, row_stride)
-from .batch import (_device_views, _resolve, aggregate_arena_tasks, check_krum_task, check_window_task, krum_rule,
-                    method_window)
+from .batch import PLUGIN, _resolve, method_route
 from .gradient_aggregation import GradientAggregationMethod
 from .model_inputs import krum_arena_tasks, robust_arena_tasks
 from .model_manager import ModelManager
+from .wave_tasks import ArenaTask, _device_views, aggregate_arena_tasks
 
 Task = Tuple[str, str, dict]  # (task_name, func_name, data with placeholders)
 
@@ -257,99 +258,71 @@ class RoundExecutor:
                 arenas = {dt: buf[o:o + n * esz].view(dt) for dt, (o, n, esz) in span.items()}
                 cache[id(m)] = (m, layout, arenas)
 
+    def _wave_task(self, models, weights, cache: dict, walked: dict) -> ArenaTask:
+        """One task's models, resolved once per wave (_arena_of), as the record the batched
+        launches read; a model whose parameter list differs from models[0]'s raises ZipMismatch."""
+        ents = [self._arena_of(m, cache, walked) for m in models]
+        layout0 = ents[0][0]
+        sig = layout0._signature
+        for i in range(1, len(ents)):
+            lay = ents[i][0]
+            if lay._signature is not sig and lay._signature != sig:
+                layout0.check_compatible(models[i])
+        views = {dt: [a[dt] for _, a in ents] for dt in layout0.groups}
+        return ArenaTask(models[0], layout0, views, weights, [lay.params for lay, _ in ents])
+
     def _aggregate_wave(self, aggs, on_launched=None) -> List[nn.Module]:
-        """One batched aggregate per dtype over the wave's tasks. on_launched:
-        see batch.aggregate_arena_tasks (the executor releases the results
-        no later task reads there, so the input modules are freed while the
+        """The wave's aggregates under settings.gradient_aggregation, equal bit
+        for bit to functions.aggregate per task (ModelManager's plugins), in
+        the batched launches batch.method_route picks: FedAvg; MEDIAN and
+        TRIMMED_MEAN; KRUM and MULTI_KRUM when ModelManager's plugin is a Krum
+        or MultiKrum class (f and m read from the class). Every task is checked
+        first and raises what its plugin raises; then the wave's models are
+        resolved (one upload of the host models, arenas and separate device
+        tensors read in place) and every task runs in one batched call per
+        dtype. The other methods and any other plugin (and an unknown value,
+        which fails as the per-task path fails) call the plugin per task on
+        the resolved models and keep the result on the device. on_launched:
+        see wave_tasks.finish_modules (the executor releases the results no
+        later task reads there, so the input modules are freed while the
         output modules are built)."""
         method = getattr(self.settings, "gradient_aggregation", GradientAggregationMethod.FEDAVG)
-        if method != GradientAggregationMethod.FEDAVG:
-            return self._aggregate_wave_method(aggs, method, on_launched)
-        cache: dict = {}
-        prepared = []
+        fedavg = method == GradientAggregationMethod.FEDAVG
         resolved = []
         for name, _, data in aggs:
             d = self._resolve(data)
-            models = d["models"]
-            ws = _resolve(models, d.get("weights"))  # fedavg.py:14-17 rules and exceptions
-            resolved.append((models, ws))
+            models, weights = d["models"], d.get("weights")
+            # FedAvg settles a task's weights as it reads the task (fedavg.py:14-17 rules and exceptions);
+            # the other methods check the whole wave once it is read
+            resolved.append((models, _resolve(models, weights) if fedavg else weights))
+        route = method_route(method, self.settings, lambda _, s: ModelManager(None, s, 0).get_aggregation_method())
+        if route.kind == PLUGIN:
+            return route.per_task(resolved)
+        for models, weights in resolved:
+            route.check(models, weights)
+        cache: dict = {}
         walked: dict = {}
         self._upload_host_models([m for models, _ in resolved for m in models], cache, walked)
+        prepared = []
         single = {}  # task position -> result of the per-parameter zip path
         for j, (models, ws) in enumerate(resolved):
-            ents = [self._arena_of(m, cache, walked) for m in models]
-            layout0 = ents[0][0]
-            sig = layout0._signature
             try:
-                for i in range(1, len(ents)):
-                    lay = ents[i][0]
-                    if lay._signature is not sig and lay._signature != sig:
-                        layout0.check_compatible(models[i])
-            except ZipMismatch:  # parameter lists differ (fedavg.py:23-24 zip)
+                prepared.append(self._wave_task(models, ws if fedavg else None, cache, walked))
+            except ZipMismatch:  # parameter lists differ: FedAvg zips (fedavg.py:23-24), the others raise it
+                if not fedavg:
+                    raise
                 single[j] = aggregate_modules(models, ws, self.mode, to_host=False)
-                continue
-            views = {dt: [a[dt] for _, a in ents] for dt in layout0.groups}
-            prepared.append((models[0], layout0, views, ws, [lay.params for lay, _ in ents]))
         n_tasks = len(resolved)
         resolved.clear()
         cache.clear()
         walked.clear()
-        outs = aggregate_arena_tasks(prepared, self.mode, on_launched)
+        # the launch functions as this module names them: a probe that times one replaces it here
+        outs = route.run(prepared, on_launched, self.mode,
+                         (aggregate_arena_tasks, robust_arena_tasks, krum_arena_tasks))
         if not single:
             return outs
         it = iter(outs)
         return [single[j] if j in single else next(it) for j in range(n_tasks)]
-
-    def _aggregate_wave_method(self, aggs, method, on_launched=None) -> List[nn.Module]:
-        """The wave's aggregates under a method other than FedAvg, equal bit
-        for bit to functions.aggregate per task (ModelManager's plugins).
-        MEDIAN and TRIMMED_MEAN resolve the wave's models as the FedAvg path
-        does (one upload of the host models, arenas and separate device
-        tensors read in place) and run every task in one batched call per
-        dtype (model_inputs.robust_arena_tasks); each task raises what its
-        plugin raises. KRUM and MULTI_KRUM, when ModelManager's plugin is a
-        Krum or MultiKrum class, resolve the models the same way and run the
-        wave in two batched phases around one synchronisation
-        (model_inputs.krum_arena_tasks), f and m read from the class. The
-        other methods and any other plugin (and an unknown value, which fails
-        as the per-task path fails) call the plugin per task on the resolved
-        models and keep the result on the device."""
-        resolved = []
-        for name, _, data in aggs:
-            d = self._resolve(data)
-            resolved.append((d["models"], d.get("weights")))
-        window = method_window(method, self.settings)
-        rule = None
-        if window is None:
-            plugin = ModelManager(None, self.settings, 0).get_aggregation_method()
-            rule = krum_rule(plugin)
-            if rule is None:
-                return [plugin.aggregate(models, weights=weights, to_host=False) for models, weights in resolved]
-        for models, weights in resolved:
-            if rule is None:
-                check_window_task(method, window, models, weights)
-            else:
-                check_krum_task(rule, models, weights)
-        cache: dict = {}
-        walked: dict = {}
-        self._upload_host_models([m for models, _ in resolved for m in models], cache, walked)
-        prepared = []
-        for models, _ in resolved:
-            ents = [self._arena_of(m, cache, walked) for m in models]
-            layout0 = ents[0][0]
-            sig = layout0._signature
-            for i in range(1, len(ents)):
-                lay = ents[i][0]
-                if lay._signature is not sig and lay._signature != sig:
-                    layout0.check_compatible(models[i])  # ZipMismatch: a ValueError, as the plugins raise
-            views = {dt: [a[dt] for _, a in ents] for dt in layout0.groups}
-            prepared.append((models[0], layout0, views, None, [lay.params for lay, _ in ents]))
-        resolved.clear()
-        cache.clear()
-        walked.clear()
-        if rule is not None:
-            return krum_arena_tasks(prepared, rule[1], rule[2], on_launched)
-        return robust_arena_tasks(prepared, window, on_launched)
 
     def run(self, tasks: Sequence[Task], seed: Optional[Dict[str, list]] = None) -> Dict[str, list]:
         """Execute `tasks`; `seed` pre-populates results (e.g. initial models).

@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     a = ap.parse_args()
     from dasklearn_amd import batch, rounds
+    from dasklearn_amd.wave_tasks import ArenaTask
 
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -66,7 +67,7 @@ def main():
             ms = d["models"]
             ents = [ex._arena_of(m, cache) for m in ms]
             views = {dt: [e[1][dt] for e in ents] for dt in ents[0][0].groups}
-            prepared.append((ms[0], ents[0][0], views, batch._resolve(ms, None), [e[0].params for e in ents]))
+            prepared.append(ArenaTask(ms[0], ents[0][0], views, batch._resolve(ms, None), [e[0].params for e in ents]))
         t_host_arena = time.perf_counter()
         sync()
         t1 = time.perf_counter()

@@ -421,12 +421,13 @@ def test_models_without_parameters_give_the_zeros_of_model_distances():
     """A task of parameterless models between two real ones: n x n zeros, as model_distances gives."""
     from dasklearn_amd.gradient_aggregation.krum import _resident_entry
     from dasklearn_amd.model_inputs import distances_arena_tasks
+    from dasklearn_amd.wave_tasks import ArenaTask
     torch.manual_seed(5)
     bare = [torch.nn.ReLU() for _ in range(4)]
     layout, params, views = arena.input_arenas(bare)
     real = [arena.to_device_arena(torch.nn.Linear(9, 7), DEV) for _ in range(3)]
     entry = _resident_entry(real, None)
-    got = distances_arena_tasks([entry, (bare[0], layout, views, None, params), entry])
+    got = distances_arena_tasks([entry, ArenaTask(bare[0], layout, views, None, params), entry])
     want = model_distances(bare, device=DEV)
     assert want.shape == (4, 4) and not want.any() and _same_matrix(got[1], want)
     assert _same_matrix(got[0], model_distances(real)) and _same_matrix(got[2], got[0])

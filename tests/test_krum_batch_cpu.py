@@ -16,6 +16,7 @@ import _edge_util as eu
 from dasklearn_amd import _native, batch, model_inputs, rounds
 from dasklearn_amd.gradient_aggregation import GradientAggregationMethod as M
 from dasklearn_amd.gradient_aggregation.krum import Krum, MultiKrum, model_distances_batch
+from dasklearn_amd.wave_tasks import ArenaTask
 
 D2 = 1 << 20  # far from every input below
 
@@ -222,7 +223,7 @@ def test_round_executor_checks_every_task_before_anything_is_queued(monkeypatch)
 def test_krum_arena_tasks_checks_before_any_device_work():
     """(n, f, m) outside the rule and more than 32 models: ValueError before a
     distance is asked for (the views are never touched)."""
-    entry = lambda n: (None, None, {torch.float32: [None] * n}, None, [None] * n)  # noqa: E731
+    entry = lambda n: ArenaTask(None, None, {torch.float32: [None] * n}, None, [None] * n)  # noqa: E731
     with pytest.raises(ValueError, match=r"n = 4 .*f = 1"):
         model_inputs.krum_arena_tasks([entry(5), entry(4)], 1, None)
     with pytest.raises(ValueError, match="m = 5"):
@@ -240,9 +241,9 @@ def test_models_without_parameters_have_a_zero_matrix():
     ms = [nn.ReLU() for _ in range(3)]
     layout, params, views = input_arenas(ms)
     assert not layout.groups and views == {} and params == [[], [], []]
-    d2, = model_inputs.distances_arena_tasks([(ms[0], layout, views, None, params)])
+    d2, = model_inputs.distances_arena_tasks([ArenaTask(ms[0], layout, views, None, params)])
     assert d2.shape == (3, 3) and d2.dtype == torch.float64 and not d2.is_cuda and not d2.any()
     with pytest.raises(ValueError, match="does not state its fan-in"):
-        model_inputs.distances_arena_tasks([(ms[0], layout, views, None)])
+        model_inputs.distances_arena_tasks([ArenaTask(ms[0], layout, views, None)])
     with pytest.raises(ValueError, match="at most 32"):
-        model_inputs.distances_arena_tasks([(ms[0], layout, views, None, [[]] * 33)])
+        model_inputs.distances_arena_tasks([ArenaTask(ms[0], layout, views, None, [[]] * 33)])
