@@ -923,17 +923,76 @@ inline int chunk_defer_rows(const std::vector<size_t>& rows, size_t cus, int rma
   return rmax;
 }
 
+// One launch of run_chunk_mean, as decided on the host (dlsim_chunk_mean_plan
+// reports these; the launch reads nothing else but the slots).
+enum ChunkMeanForm : int {
+  kCmFormTiledFew = 0,  // k_chunk_mean_batch<CmFewRows>
+  kCmFormTiled,         // k_chunk_mean_batch<CmDefault>
+  kCmFormTable,         // k_chunk_mean_table (m > kCmMaxPtrs, one task)
+  kCmFormDeferRf4,      // k_chunk_mean_defer<CmFewRows::RF>
+  kCmFormDeferRf8,      // k_chunk_mean_defer<CmDefault::RF>
+  kCmFormDeferM         // k_chunk_mean_defer_m<MF>
+};
+struct ChunkMeanPlan {
+  int form;
+  int mf;   // kCmFormDeferM: the launch's contributor count, else 0
+  int R;    // rows per block of a deferred form, else 0
+  int bpt;  // kCmFormDeferM: blocks of every task but the last when equal, else 0
+  unsigned grid;
+  int ntasks;
+  int first_task;  // index in the call's task list
+};
+
+// The launch of one decided kernel-argument batch (every form but the table).
+template <class Op>
+int launch_chunk_plan(const ChunkMeanPlan& pl, const dlsim::ChunkMeanSlots& s, hipStream_t st) {
+  const dim3 grid(pl.grid);
+  switch (pl.form) {
+    case kCmFormTiledFew:
+      hipLaunchKernelGGL((dlsim::k_chunk_mean_batch<Op, CmFewRows>), grid, dim3(dlsim::kBlock), 0, st, s);
+      break;
+    case kCmFormTiled:
+      hipLaunchKernelGGL((dlsim::k_chunk_mean_batch<Op, CmDefault>), grid, dim3(dlsim::kBlock), 0, st, s);
+      break;
+    default:
+      if constexpr (Op::kBytes == 4) {
+        if (pl.form == kCmFormDeferM) {
+          const hipError_t e = launch_chunk_defer_m<Op, kCmFixedMinM>(s, pl.mf, pl.R, pl.bpt, pl.grid, st);
+          if (e != hipSuccess) return hip_fail(e, "chunk mean batch launch");
+        } else if (pl.form == kCmFormDeferRf4) {
+          hipLaunchKernelGGL((dlsim::k_chunk_mean_defer<Op, CmFewRows::RF, kCmDeferRMax, kCmDeferU>), grid,
+                             dim3(dlsim::kDeferBlock), 0, st, s, pl.R);
+        } else if (pl.form == kCmFormDeferRf8) {
+          hipLaunchKernelGGL((dlsim::k_chunk_mean_defer<Op, CmDefault::RF, kCmDeferRMax, kCmDeferU>), grid,
+                             dim3(dlsim::kDeferBlock), 0, st, s, pl.R);
+        } else {
+          return fail(DLSIM_E_ARG, "chunk mean plan: form %d is no batch launch", pl.form);
+        }
+      } else {
+        return fail(DLSIM_E_ARG, "chunk mean plan: form %d needs 4-byte elements", pl.form);
+      }
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "chunk mean batch launch");
+  return DLSIM_OK;
+}
+
+// plan != nullptr: decide only (one record per launch the call would make, in
+// launch order; no pointer is read, no stream touched). cus > 0 stands for
+// device_cus().
 template <class Op>
 int run_chunk_mean(int b, const int* fan_in, const void* const* in, void* const* outs, const size_t* nelem,
-                   int threads, hipStream_t st) {
+                   int threads, hipStream_t st, std::vector<ChunkMeanPlan>* plan = nullptr, int cus = 0) {
   constexpr size_t tile = static_cast<size_t>(dlsim::kBlock) * CmDefault::VPT;
   std::vector<size_t> off(static_cast<size_t>(b) + 1, 0);
   for (int t = 0; t < b; ++t) off[t + 1] = off[t] + static_cast<size_t>(fan_in[t]);
   if (b > 1 && cross_task_overlap(b, fan_in, in, outs, nelem, Op::kBytes)) {
     // tasks touch each other's outputs: one launch per task, in order
     for (int t = 0; t < b; ++t) {
-      int rc = run_chunk_mean<Op>(1, fan_in + t, in + off[t], outs + t, nelem + t, threads, st);
+      const size_t before = plan ? plan->size() : 0;
+      int rc = run_chunk_mean<Op>(1, fan_in + t, in + off[t], outs + t, nelem + t, threads, st, plan, cus);
       if (rc != DLSIM_OK) return rc;
+      for (size_t k = before; plan && k < plan->size(); ++k) (*plan)[k].first_task += t;
     }
     return DLSIM_OK;
   }
@@ -975,12 +1034,12 @@ int run_chunk_mean(int b, const int* fan_in, const void* const* in, void* const*
   std::vector<CmTask> batch;
   int np = 0;
   size_t tiles = 0;  // the tiled kernel's grid for the batch so far
-  auto flush = [&]() -> int {
-    if (batch.empty()) return DLSIM_OK;
-    dlsim::ChunkMeanSlots s;
+  auto ncus = [&]() { return static_cast<size_t>(cus > 0 ? cus : device_cus()); };
+  // The pending batch's launch: its form and grid into pl, its tasks into s.
+  auto decide = [&](dlsim::ChunkMeanSlots& s, ChunkMeanPlan& pl) -> int {
     std::memset(&s, 0, sizeof(s));
     // deferred stores: fp32, every task vector-aligned with m >= 16 (or every
-    // task with one m, 2 <= m < 16: the fixed-m form), >= 20 MB per stream
+    // task with one m, 4 <= m < 16: the fixed-m form), >= 20 MB per stream
     bool defer = Op::kBytes == 4 && chunk_defer_on();
     bool fixed = std::is_same<Op, dlsim::F32Mean>::value && chunk_defer_on() && chunk_defer_fixed_on();
     const int m0 = fan_in[batch.front().t];
@@ -998,9 +1057,9 @@ int run_chunk_mean(int b, const int* fan_in, const void* const* in, void* const*
     fixed = fixed && defer;
     int R = 0;
     if (fixed)
-      R = chunk_defer_m_rows(rows, static_cast<size_t>(device_cus()), cm_defer_m_rmax(m0));
+      R = chunk_defer_m_rows(rows, ncus(), cm_defer_m_rmax(m0));
     else if (defer)
-      R = chunk_defer_rows(rows, static_cast<size_t>(device_cus()));
+      R = chunk_defer_rows(rows, ncus());
     size_t blocks = 0;
     int nt = 0, p = 0;
     for (const CmTask& k : batch) {
@@ -1025,31 +1084,34 @@ int run_chunk_mean(int b, const int* fan_in, const void* const* in, void* const*
     s.ntasks = nt;
     s.block_start[nt] = static_cast<uint32_t>(fixed ? blocks : blocks - static_cast<size_t>(nt));
     if (blocks > 0x7fffffffu) return fail(DLSIM_E_ARG, "chunk mean batch too large");
-    if (defer) {
-      if constexpr (Op::kBytes == 4) {
-        const unsigned grid = static_cast<unsigned>(blocks);
-        if (fixed) {
-          int bpt = static_cast<int>(nt > 1 ? s.block_start[1] - s.block_start[0] : s.block_start[1]);
-          for (int k = 1; bpt > 0 && k + 1 < nt; ++k)
-            if (s.block_start[k + 1] - s.block_start[k] != static_cast<uint32_t>(bpt)) bpt = 0;
-          const hipError_t e = launch_chunk_defer_m<Op, 2>(s, m0, R, bpt, grid, st);
-          if (e != hipSuccess) return hip_fail(e, "chunk mean batch launch");
-        } else if (few_rows)
-          hipLaunchKernelGGL((dlsim::k_chunk_mean_defer<Op, CmFewRows::RF, kCmDeferRMax, kCmDeferU>), dim3(grid),
-                             dim3(dlsim::kDeferBlock), 0, st, s, R);
-        else
-          hipLaunchKernelGGL((dlsim::k_chunk_mean_defer<Op, CmDefault::RF, kCmDeferRMax, kCmDeferU>), dim3(grid),
-                             dim3(dlsim::kDeferBlock), 0, st, s, R);
-      }
-    } else if (few_rows) {
-      hipLaunchKernelGGL((dlsim::k_chunk_mean_batch<Op, CmFewRows>), dim3(static_cast<unsigned>(blocks)),
-                         dim3(dlsim::kBlock), 0, st, s);
-    } else {
-      hipLaunchKernelGGL((dlsim::k_chunk_mean_batch<Op, CmDefault>), dim3(static_cast<unsigned>(blocks)),
-                         dim3(dlsim::kBlock), 0, st, s);
+    pl = ChunkMeanPlan{};
+    pl.form = fixed ? kCmFormDeferM
+                    : defer ? (few_rows ? kCmFormDeferRf4 : kCmFormDeferRf8) : few_rows ? kCmFormTiledFew : kCmFormTiled;
+    pl.R = R;
+    pl.grid = static_cast<unsigned>(blocks);
+    pl.ntasks = nt;
+    pl.first_task = batch.front().t;
+    if (fixed) {
+      int bpt = static_cast<int>(nt > 1 ? s.block_start[1] - s.block_start[0] : s.block_start[1]);
+      for (int k = 1; bpt > 0 && k + 1 < nt; ++k)
+        if (s.block_start[k + 1] - s.block_start[k] != static_cast<uint32_t>(bpt)) bpt = 0;
+      pl.mf = m0;
+      pl.bpt = bpt;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "chunk mean batch launch");
+    return DLSIM_OK;
+  };
+  auto flush = [&]() -> int {
+    if (batch.empty()) return DLSIM_OK;
+    dlsim::ChunkMeanSlots s;
+    ChunkMeanPlan pl;
+    int rc = decide(s, pl);
+    if (rc != DLSIM_OK) return rc;
+    if (plan) {
+      plan->push_back(pl);
+    } else {
+      rc = launch_chunk_plan<Op>(pl, s, st);
+      if (rc != DLSIM_OK) return rc;
+    }
     batch.clear();
     np = 0;
     tiles = 0;
@@ -1064,6 +1126,10 @@ int run_chunk_mean(int b, const int* fan_in, const void* const* in, void* const*
     const uint32_t head = m > dlsim::kCmMaxPtrs ? 0u : task_head(t, ib, flags);
     const size_t tb = task_blocks(ib, head);
     if (m > dlsim::kCmMaxPtrs) {
+      if (plan) {
+        plan->push_back(ChunkMeanPlan{kCmFormTable, 0, 0, 0, static_cast<unsigned>(tb), 1, t});
+        continue;
+      }
       // input pointers through a stream-ordered device array (any m)
       void* d = nullptr;
       const size_t bytes = static_cast<size_t>(m) * sizeof(void*);
@@ -1110,14 +1176,14 @@ int run_chunk_mean(int b, const int* fan_in, const void* const* in, void* const*
   X int dlsim_host::run_batched<Op>(int, const int*, const void* const*, const float*, void* const*,    \
                                     const size_t*, hipStream_t, const float*);                          \
   X int dlsim_host::run_chunk_mean<Op>(int, const int*, const void* const*, void* const*, const size_t*, \
-                                       int, hipStream_t);
+                                       int, hipStream_t, std::vector<dlsim_host::ChunkMeanPlan>*, int);
 #define DLSIM_PROBE_ENTRIES(X, Op) \
   X int dlsim_host::run<Op>(const void* const*, int, const float*, void*, size_t, hipStream_t, float);
 #define DLSIM_F64_ENTRIES(X, Op) \
   X int dlsim_host::run<Op>(const void* const*, int, const double*, void*, size_t, hipStream_t, float);
 #define DLSIM_CHUNK_ENTRIES(X, Op)                                                                       \
   X int dlsim_host::run_chunk_mean<Op>(int, const int*, const void* const*, void* const*, const size_t*, \
-                                       int, hipStream_t);
+                                       int, hipStream_t, std::vector<dlsim_host::ChunkMeanPlan>*, int);
 
 // every policy's entries, with X = `extern template` (declare) or `template` (define)
 #define DLSIM_ALL_ENTRIES(X)                  \

@@ -529,9 +529,10 @@ size_t dlsim_chunk_mean_ilp_begin(int m, size_t n_elems, int cpu_threads) {
   return chunk_mean_ilp_begin(m, n_elems, cpu_threads);
 }
 
-int dlsim_chunk_mean_batched(int b, const int* fan_in, const void* const* d_inputs, void* const* d_outs,
-                             const size_t* n_elems, int dtype, int cpu_threads, void* stream) {
-  g_err.clear();
+// Argument checks shared by dlsim_chunk_mean_batched and dlsim_chunk_mean_plan
+// (addresses and sizes only; nothing is read through a buffer pointer).
+static int check_chunk_mean_args(int b, const int* fan_in, const void* const* d_inputs, void* const* d_outs,
+                                 const size_t* n_elems, int dtype, int cpu_threads) {
   if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
   if (b == 0) return DLSIM_OK;
   if (!fan_in || !d_inputs || !d_outs || !n_elems) return fail(DLSIM_E_ARG, "null array argument");
@@ -545,10 +546,44 @@ int dlsim_chunk_mean_batched(int b, const int* fan_in, const void* const* d_inpu
       return fail(DLSIM_E_ARG, "task %d: chunk of %zu elements is >= 2 GiB", t, n_elems[t]);
     off += static_cast<size_t>(fan_in[t]);
   }
+  return DLSIM_OK;
+}
+
+int dlsim_chunk_mean_batched(int b, const int* fan_in, const void* const* d_inputs, void* const* d_outs,
+                             const size_t* n_elems, int dtype, int cpu_threads, void* stream) {
+  g_err.clear();
+  const int rc = check_chunk_mean_args(b, fan_in, d_inputs, d_outs, n_elems, dtype, cpu_threads);
+  if (rc != DLSIM_OK || b == 0) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return with_chunk_policy(dtype, [&](auto op) {
     return run_chunk_mean<decltype(op)>(b, fan_in, d_inputs, d_outs, n_elems, cpu_threads, st);
   });
+}
+
+int dlsim_chunk_mean_plan(int b, const int* fan_in, const void* const* d_inputs, void* const* d_outs,
+                          const size_t* n_elems, int dtype, int cpu_threads, int cus,
+                          dlsim_chunk_launch* records, int max_records, int* n_records) {
+  g_err.clear();
+  if (cus < 0 || max_records < 0 || !n_records || (max_records > 0 && !records))
+    return fail(DLSIM_E_ARG, "need cus >= 0, max_records >= 0, n_records and a records array");
+  *n_records = 0;
+  int rc = check_chunk_mean_args(b, fan_in, d_inputs, d_outs, n_elems, dtype, cpu_threads);
+  if (rc != DLSIM_OK || b == 0) return rc;
+  static_assert(DLSIM_CHUNK_TILED_FEW == kCmFormTiledFew && DLSIM_CHUNK_TILED == kCmFormTiled &&
+                    DLSIM_CHUNK_TABLE == kCmFormTable && DLSIM_CHUNK_DEFER_RF4 == kCmFormDeferRf4 &&
+                    DLSIM_CHUNK_DEFER_RF8 == kCmFormDeferRf8 && DLSIM_CHUNK_DEFER_M == kCmFormDeferM,
+                "dlsim.h names dispatch.hpp's forms");
+  std::vector<ChunkMeanPlan> plan;  // run_chunk_mean's own decisions, nothing launched
+  rc = with_chunk_policy(dtype, [&](auto op) {
+    return run_chunk_mean<decltype(op)>(b, fan_in, d_inputs, d_outs, n_elems, cpu_threads, nullptr, &plan, cus);
+  });
+  if (rc != DLSIM_OK) return rc;
+  *n_records = static_cast<int>(plan.size());
+  for (int k = 0; k < *n_records && k < max_records; ++k) {
+    const ChunkMeanPlan& q = plan[static_cast<size_t>(k)];
+    records[k] = dlsim_chunk_launch{q.form, q.mf, q.R, q.bpt, q.grid, q.ntasks, q.first_task};
+  }
+  return DLSIM_OK;
 }
 
 int dlsim_host_wreduce(int n, int t, const void* const* h_srcs, const size_t* numels,

@@ -53,6 +53,7 @@ EXPORTS = (
     "dlsim_mean_batched",
     "dlsim_chunk_mean_batched",
     "dlsim_chunk_mean_ilp_begin",
+    "dlsim_chunk_mean_plan",
     "dlsim_rccl_bind",
     "dlsim_wreduce_sharded",
     "dlsim_wreduce_sharded_f64",
@@ -97,6 +98,15 @@ EXPORTS = (
 
 _lib = None
 _lock = threading.Lock()
+
+
+class ChunkLaunch(ctypes.Structure):
+    """dlsim_chunk_launch (include/dlsim.h): one launch of a chunk-mean call."""
+    _fields_ = [("form", ctypes.c_int), ("mf", ctypes.c_int), ("rows", ctypes.c_int), ("bpt", ctypes.c_int),
+                ("grid", ctypes.c_uint), ("ntasks", ctypes.c_int), ("first_task", ctypes.c_int)]
+
+
+CHUNK_FORMS = ("tiled_few", "tiled", "table", "defer_rf4", "defer_rf8", "defer_m")  # DLSIM_CHUNK_*
 
 
 class DlsimError(RuntimeError):
@@ -153,6 +163,10 @@ def load() -> ctypes.CDLL:
         lib.dlsim_chunk_mean_batched.restype = i
         lib.dlsim_chunk_mean_ilp_begin.argtypes = [i, sz, i]
         lib.dlsim_chunk_mean_ilp_begin.restype = sz
+        lib.dlsim_chunk_mean_plan.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                              ctypes.POINTER(sz), i, i, i, ctypes.POINTER(ChunkLaunch), i,
+                                              ctypes.POINTER(i)]
+        lib.dlsim_chunk_mean_plan.restype = i
         lib.dlsim_rccl_bind.argtypes = [ctypes.c_char_p]
         lib.dlsim_rccl_bind.restype = i
         lib.dlsim_wreduce_sharded.argtypes = [ctypes.POINTER(vp), sz, i, ctypes.POINTER(ctypes.c_float), vp, sz, i,
@@ -1270,6 +1284,50 @@ class ShardedPlan:
 def chunk_mean_ilp_begin(m: int, n: int, threads: int) -> int:
     """Host rule of dlsim_chunk_mean_batched (no GPU needed)."""
     return int(load().dlsim_chunk_mean_ilp_begin(m, n, threads))
+
+
+def chunk_mean_plan(tasks, threads: int, cus: int = 0, dtype=None):
+    """The launches chunk_mean_batched(tasks, threads) would make
+    (dlsim_chunk_mean_plan: decided by the launching code, nothing launched,
+    no pointer read). tasks: (inputs, out) tensors as chunk_mean_batched
+    takes them, or (input addresses, output address, numel) integers of
+    `dtype` (default torch.float32), which only need the alignment and spacing
+    of real buffers. cus > 0 stands for the device's CU count (no GPU
+    needed); 0 asks the device. Returns one dict per launch, in launch order:
+    form (one of CHUNK_FORMS), mf, R, bpt, grid, ntasks, first_task."""
+    import torch
+    lib = load()
+    fan, ptrs, outs, numels = [], [], [], []
+    for task in tasks:
+        if len(task) == 3:
+            ins, out, n = task
+            dt = torch.float32 if dtype is None else dtype
+            ptrs.extend(int(q) for q in ins)
+            outs.append(int(out))
+        else:
+            ins, out = task
+            n, dt = out.numel(), out.dtype
+            if dtype is not None and dt != dtype:
+                raise ValueError("a task's tensors are not of `dtype`")
+            ptrs.extend(t.data_ptr() for t in ins)
+            outs.append(out.data_ptr())
+        dtype = dt
+        fan.append(len(ins))
+        numels.append(int(n))
+    b = len(fan)
+    if b == 0:
+        return []
+    cap = b + 1  # every launch holds at least one task
+    recs = (ChunkLaunch * cap)()
+    count = ctypes.c_int(0)
+    _check("dlsim_chunk_mean_plan",
+           lib.dlsim_chunk_mean_plan(b, (ctypes.c_int * b)(*fan), (ctypes.c_void_p * len(ptrs))(*ptrs),
+                                     (ctypes.c_void_p * b)(*outs), (ctypes.c_size_t * b)(*numels),
+                                     dtype_code(dtype, single_task=True), int(threads), int(cus), recs, cap,
+                                     ctypes.byref(count)))
+    assert count.value <= cap
+    return [{"form": CHUNK_FORMS[r.form], "mf": r.mf, "R": r.rows, "bpt": r.bpt, "grid": r.grid,
+             "ntasks": r.ntasks, "first_task": r.first_task} for r in recs[:count.value]]
 
 
 def wreduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], weights_f32, out_ptrs: Sequence[int],

@@ -249,6 +249,39 @@ int dlsim_chunk_mean_batched(int b, const int* fan_in, const void* const* d_inpu
 size_t dlsim_chunk_mean_ilp_begin(int m, size_t n_elems, int cpu_threads);
 
 /*
+ * dlsim_chunk_mean_plan — the launches dlsim_chunk_mean_batched would make for
+ * these arguments, one record per launch in launch order, decided by the code
+ * that launches (host only: no pointer is read through, no stream is touched,
+ * so the addresses only need the alignment and spacing of real buffers).
+ * cus > 0 stands for the device's compute-unit count, so the query runs
+ * without a GPU; cus == 0 asks the current device. The DLSIM_AB switches of
+ * the launch apply. A diagnostic in the spirit of dlsim_kernel_name, for
+ * tests that must know which kernel a case reaches. *n_records gets the
+ * number of launches; the first min(*n_records, max_records) are written.
+ * (New: no reference counterpart.)
+ */
+enum {
+  DLSIM_CHUNK_TILED_FEW = 0, /* tiled kernel, 4 rows per load group (every m <= 6) */
+  DLSIM_CHUNK_TILED = 1,     /* tiled kernel, 8 rows per load group */
+  DLSIM_CHUNK_TABLE = 2,     /* one task of m > 192: pointers in device memory */
+  DLSIM_CHUNK_DEFER_RF4 = 3, /* deferred stores, runtime m, 4 rows per load group */
+  DLSIM_CHUNK_DEFER_RF8 = 4, /* deferred stores, runtime m, 8 rows per load group */
+  DLSIM_CHUNK_DEFER_M = 5    /* deferred stores, one compile-time m (4..15) for every task */
+};
+typedef struct dlsim_chunk_launch {
+  int form;        /* DLSIM_CHUNK_* */
+  int mf;          /* DLSIM_CHUNK_DEFER_M: the contributor count, else 0 */
+  int rows;        /* deferred forms: R, rows of 512 16-byte vectors a block folds before it stores; else 0 */
+  int bpt;         /* DLSIM_CHUNK_DEFER_M: blocks of every task but the last when they are equal, else 0 */
+  unsigned grid;   /* blocks of the launch */
+  int ntasks;      /* tasks of the launch */
+  int first_task;  /* index of its first task in the call */
+} dlsim_chunk_launch;
+int dlsim_chunk_mean_plan(int b, const int* fan_in, const void* const* d_inputs, void* const* d_outs,
+                          const size_t* n_elems, int dtype, int cpu_threads, int cus,
+                          dlsim_chunk_launch* records, int max_records, int* n_records);
+
+/*
  * dlsim_rccl_bind — dlopen the RCCL library whose communicators will be
  * passed to dlsim_wreduce_sharded (the library does not link RCCL, so a
  * process keeps one RCCL instance: from PyTorch, torch/lib/librccl.so, whose

@@ -646,6 +646,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--only", default=None, help="comma-separated families (default: all, weighted)")
+    ap.add_argument("--large-chunk-rate", type=float, default=0.02,
+                    help="share of the fp32 chunk_mean cases that are one launch of >= 20 MB per stream")
     a = ap.parse_args()
     only = a.only.split(",") if a.only else None
     rng = np.random.default_rng(a.seed)
@@ -653,6 +655,7 @@ def main():
               "reconstruct": 0, "host_reduce": 0, "host_chunk": 0, "executor": 0, "cached": 0, "sharded": 0, "sgd": 0, "sgdm": 0,
               "robust": 0, "robust_batch": 0, "krum_batch": 0}
     fails = []
+    large_chunk_launches = []  # the rare >= 20 MB chunk-mean launches: what was drawn and the forms they took
     t_end = time.time() + a.seconds
     t_note = time.time() + 20
     while time.time() < t_end and len(fails) < 10:
@@ -929,20 +932,39 @@ def main():
             else:
                 threads = int(rng.choice([1, 2, 4, 8, 16]))
                 tasks, exps, guards = [], [], []
+                shapes = []
                 for _ in range(int(rng.integers(1, 24))):
                     m = int(rng.choice([1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 31, 33, 64, 100, 250]))
                     n = int(rng.choice([1, 2, 3, 4, 7, 8, 9, 31, 32, 33, 95, 1000, 8193, 100_003]))
                     if m * n > 1_000_000:  # keeps one case's oracle work to well under a second
                         n = int(rng.choice([1, 7, 33, 1000]))
+                    shapes.append((m, n, int(rng.choice([0, 0, 0, 1]))))
+                large = None
+                if dtype == "f32" and rng.random() < a.large_chunk_rate:
+                    # Rare and heavy (seconds of oracle work): one aligned launch of at least 20 MB per
+                    # stream with one m for every task, the only size at which run_chunk_mean takes its
+                    # deferred-store kernels (the launches above stay under 10 MB).
+                    m = int(rng.choice(list(range(4, 18)) + [33]))
+                    k = int(rng.integers(1, min(10, 192 // m) + 1))
+                    total = 5_000_000 + 4 * int(rng.integers(0, 50_000))
+                    cuts = sorted({int(c) // 4 * 4 for c in rng.integers(1, total, size=k - 1)} - {0})
+                    shapes = [(m, e - b, 0) for b, e in zip([0] + cuts, cuts + [total])]
+                    large = dict(m=m, tasks=len(shapes), columns=total, threads=threads)
+                for m, n, off in shapes:
                     rows = rand_values(rng, m, n, dtype)
-                    xs = to_dev(rows, dtype, int(rng.choice([0, 0, 0, 1])))
+                    xs = to_dev(rows, dtype, off)
                     guards.append(eu.guarded(n * eu.ESIZE[dtype], dtype, "cuda"))
                     tasks.append((xs, guards[-1].view))
                     exps.append(orc.chunk_mean(list(rows), dtype, threads))
+                if large is not None:
+                    large["forms"] = [q["form"] for q in _native.chunk_mean_plan(tasks, threads)]
+                    large_chunk_launches.append(large)
                 _native.chunk_mean_batched(tasks, threads=threads)
                 ok = all(orc.same_bits(bits(t[1]), e) for t, e in zip(tasks, exps))
                 counts["chunk_mean"] += 1
                 case = dict(kind="chunk_mean", dtype=dtype, tasks=len(tasks), threads=threads)
+                if large is not None:
+                    case["large"] = large
                 dirty = [(i, d) for i, g in enumerate(guards) for d in eu.check_guards(g, limit=4)]
                 if dirty:
                     ok, case["guard_bytes_written"] = False, dirty[:8]
@@ -951,7 +973,8 @@ def main():
         if not ok:
             fails.append(case)
     torch.cuda.synchronize()
-    print(json.dumps({"seconds": a.seconds, "seed": a.seed, "cases": counts, "failures": fails}), flush=True)
+    print(json.dumps({"seconds": a.seconds, "seed": a.seed, "cases": counts,
+                      "large_chunk_launches": large_chunk_launches, "failures": fails}), flush=True)
     sys.exit(1 if fails else 0)
 
 

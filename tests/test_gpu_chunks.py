@@ -460,9 +460,11 @@ def test_chunk_mean_deferred_launch(m, k):
     chunks of a 6.3 M-element flat model cut at arbitrary points
     (line-misaligned heads, partial rows, scalar tails), the level-1 flush at
     16 rows (m = 16, 17, 31), launches split at the 192-input limit (m = 40:
-    some below 20 MB, tiled), m = 5 tiled: every element bit-identical to the
-    order-exact oracle at 4 worker threads. (Round 6: m = 5 now takes the
-    fixed-m form, k_chunk_mean_defer_m.)"""
+    launches of 4 and 2 tasks, both below 20 MB, so both tiled; m = 40 on the
+    deferred kernel is in test_gpu_chunk_defer_matrix.py), m = 5 on the fixed-m
+    form, k_chunk_mean_defer_m: every element bit-identical to the order-exact
+    oracle at 4 worker threads. The plan query is asserted first, so a case
+    that misses the kernel it names fails."""
     P = 6_300_001
     g = torch.Generator(device=dev()).manual_seed(m * 100 + k)
     flats = [torch.randn(P, generator=g, device=dev()) * 0.05 for _ in range(m)]
@@ -470,6 +472,15 @@ def test_chunk_mean_deferred_launch(m, k):
     cuts = sorted(set(int(c) // 4 * 4 for c in rng.integers(1, P - 1, size=k - 1)))
     bounds = list(zip([0] + cuts, cuts + [P]))
     tasks = [([f[b:e] for f in flats], torch.empty(e - b, device=dev())) for b, e in bounds]
+    plan = _native.chunk_mean_plan(tasks, 4)
+    if m == 5:  # one fixed-m launch
+        assert [(q["form"], q["mf"], q["ntasks"]) for q in plan] == [("defer_m", 5, len(tasks))], plan
+    elif m == 40:  # 4 tasks of 40 inputs per launch: 13.8 MB and 11.4 MB per stream, both under 20 MB
+        assert [(q["form"], q["ntasks"], q["first_task"]) for q in plan] == [("tiled", 4, 0), ("tiled", 2, 4)], plan
+        assert all(sum(e - b for b, e in bounds[lo:hi]) * 4 < 20_000_000 for lo, hi in ((0, 4), (4, 6)))
+    else:
+        assert [(q["form"], q["ntasks"]) for q in plan] == [("defer_rf8", len(tasks))], plan
+    assert all(q["R"] >= 4 for q in plan if q["form"] != "tiled"), plan
     _native.chunk_mean_batched(tasks, threads=4)
     host = [f.cpu().numpy() for f in flats]
     for (b, e), (_, out) in zip(bounds, tasks):
@@ -487,8 +498,11 @@ def test_chunk_mean_fixed_m_deferred_launch(m, k):
     last row block also doing its ragged end). Arbitrary cuts plus a tiny
     chunk (no whole row: only the last-block ragged work), a chunk of whole
     rows exactly, line-misaligned heads and scalar tails: every element
-    bit-identical to the order-exact oracle at 4 worker threads."""
-    P = 6_300_001 if m < 12 else 3_900_001
+    bit-identical to the order-exact oracle at 4 worker threads. P is
+    6,300,001 (25.2 MB per stream) for every m: a launch under 20 MB runs the
+    tiled kernel whatever its m, so the plan query is asserted first (one
+    defer_m launch with MF = m; m = 2: one tiled launch)."""
+    P = 6_300_001
     g = torch.Generator(device=dev()).manual_seed(m * 1000 + k)
     flats = [torch.randn(P, generator=g, device=dev()) * 0.05 for _ in range(m)]
     rng = np.random.default_rng(m * 7 + k)
@@ -499,6 +513,12 @@ def test_chunk_mean_fixed_m_deferred_launch(m, k):
     cuts = sorted(c for c in cuts if 0 < c < P)
     bounds = list(zip([0] + cuts, cuts + [P]))
     tasks = [([f[b:e] for f in flats], torch.empty(e - b, device=dev())) for b, e in bounds]
+    plan = _native.chunk_mean_plan(tasks, 4)
+    if m >= 4:
+        assert [(q["form"], q["mf"], q["ntasks"]) for q in plan] == [("defer_m", m, len(tasks))], plan
+        assert 4 <= plan[0]["R"] <= (24 if m >= 12 else 32), plan
+    else:
+        assert [(q["form"], q["ntasks"]) for q in plan] == [("tiled_few", len(tasks))], plan
     _native.chunk_mean_batched(tasks, threads=4)
     host = [f.cpu().numpy() for f in flats]
     for (b, e), (_, out) in zip(bounds, tasks):

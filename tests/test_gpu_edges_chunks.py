@@ -122,7 +122,12 @@ def test_deferred_forms_at_the_smallest_deferring_launch(m):
             flat[:, b + q:b + q + ww] = block[:, :ww]
     flats = [torch.from_numpy(r).to(dev()) for r in flat]
     h = eu.guarded_many([e - b for b, e in bounds], "f32", dev(), gap=16)
-    _native.chunk_mean_batched([([f[b:e] for f in flats], v) for (b, e), v in zip(bounds, h.views)], threads=threads)
+    tasks = [([f[b:e] for f in flats], v) for (b, e), v in zip(bounds, h.views)]
+    plan = _native.chunk_mean_plan(tasks, threads)
+    want = ("defer_rf8", 0, 4) if m == 16 else ("defer_m", m, 4)
+    assert [(q["form"], q["mf"], q["ntasks"]) for q in plan] == [want], plan
+    assert plan[0]["bpt"] == 0 and 4 <= plan[0]["R"] <= (24 if m == 12 else 32), plan  # unequal tasks: the search
+    _native.chunk_mean_batched(tasks, threads=threads)
     torch.cuda.synchronize()
     assert eu.check_guards(h) == []
     for k, (b, e) in enumerate(bounds):
