@@ -307,7 +307,8 @@ bool sgdm_cross_overlap(int t, const void* const* p, const void* const* g, const
 }
 
 // The dispatches of the entries over n <= 32 inputs (inst_robust.hip,
-// inst_pairdist.hip, inst_pairdist_batch.hip, inst_reducedist.hip): arguments already checked.
+// inst_pairdist.hip, inst_pairdist_batch.hip, inst_reducedist.hip, inst_reducedist_batch.hip):
+// arguments already checked.
 hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
                        hipStream_t st);
 hipError_t robust_batched(int b, const int* fan_in, const void* const* in, const int* lo, const int* hi,
@@ -321,6 +322,10 @@ hipError_t pairdist_batched(int b, const int* fan_in, const int* n_tensors, cons
 hipError_t reducedist_flat(const void* const* in, int n, const double* w, void* out, size_t nelem, int dtype,
                            double* d2, int accumulate, hipStream_t st);
 void reducedist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
+hipError_t reducedist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* in,
+                              const size_t* nelem, const size_t* out_off, const double* w, void* const* outs,
+                              int dtype, double* const* d2s, int accumulate, hipStream_t st);
+void reducedist_batch_geometry(int dtype, int* max_segments, int* max_ptrs);
 
 // why each family stops at its DLSIM_MAX_*_INPUTS (check_fan_in, fanin_checks.hpp)
 constexpr const char* kRobustLimit = "the sorting network is held in registers";
@@ -1443,6 +1448,30 @@ int dlsim_reducedist_geometry(int n, int dtype, size_t n_elems, size_t* tile_ele
   if (rc != DLSIM_OK) return rc;
   if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
   reducedist_geometry(n, dtype, n_elems, tile_elems, blocks);
+  return DLSIM_OK;
+}
+
+int dlsim_wreduce_dist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* d_inputs,
+                               const size_t* n_elems, const size_t* out_off_bytes, const double* h_weights,
+                               void* const* d_out, int dtype, double* const* d_d2, int accumulate, void* stream) {
+  g_err.clear();
+  if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
+  if (b == 0) return DLSIM_OK;
+  if (!fan_in || !n_tensors || !d_out || !d_d2) return fail(DLSIM_E_ARG, "null array argument");
+  const int rc = check_reducedist_tasks(b, fan_in, n_tensors, d_inputs, n_elems, out_off_bytes, h_weights, d_out, d_d2,
+                                        DLSIM_MAX_REDUCEDIST_INPUTS, dtype, accumulate, kReducedistLimit);
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = reducedist_batched(b, fan_in, n_tensors, d_inputs, n_elems, out_off_bytes, h_weights, d_out,
+                                          dtype, d_d2, accumulate, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "reduce-and-measure launch");
+}
+
+int dlsim_reducedist_batch_geometry(int n, int dtype, int* max_segments, int* max_ptrs) {
+  g_err.clear();
+  const int rc = check_fan_in(n, DLSIM_MAX_REDUCEDIST_INPUTS, dtype, kReducedistLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!max_segments || !max_ptrs) return fail(DLSIM_E_ARG, "null result pointer");
+  reducedist_batch_geometry(dtype, max_segments, max_ptrs);
   return DLSIM_OK;
 }
 

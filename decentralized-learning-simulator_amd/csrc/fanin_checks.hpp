@@ -4,6 +4,8 @@
 #pragma once
 
 #include <algorithm>
+#include <cstdio>
+#include <string>
 #include <vector>
 
 #include "abi_common.hpp"
@@ -130,6 +132,88 @@ inline int check_pairdist_tasks(int b, const int* fan_in, const int* n_tensors, 
         if (it != mats.end() && it->a < a1)
           return fail(DLSIM_E_ARG, "task %d, tensor %d: the distance matrix of task %d overlaps input %d", k, j,
                       it->task, i);
+      }
+    }
+    po += static_cast<size_t>(n) * static_cast<size_t>(t);
+    lo += static_cast<size_t>(t);
+  }
+  return DLSIM_OK;
+}
+
+// The task list of dlsim_wreduce_dist_batched: task k reads fan_in[k] * n_tensors[k] pointers,
+// model-major, n_tensors[k] lengths and output offsets and fan_in[k] weights at the running offsets,
+// writes fan_in[k] doubles at d2[k] and, unless outs[k] is null, every non-empty tensor's range at
+// outs[k] + out_off. dtype and accumulate first; then per task, in order: 1 <= fan_in <= max,
+// n_tensors >= 0, a non-null vector, weights that survive fp32 (fp64 buffers take any); then what the
+// call writes (vectors and output ranges) against each other, and every non-empty tensor of every
+// task (no null pointer) against all of it: no byte shared.
+inline int check_reducedist_tasks(int b, const int* fan_in, const int* n_tensors, const void* const* in,
+                                  const size_t* n_elems, const size_t* out_off, const double* w, void* const* outs,
+                                  double* const* d2, int max, int dtype, int accumulate, const char* reason) {
+  if (!known_dtype(dtype) && dtype != DLSIM_F64) return fail(DLSIM_E_DTYPE, "unsupported dtype %d", dtype);
+  int rc = check_accumulate(accumulate);
+  if (rc != DLSIM_OK) return rc;
+  if (!w) return fail(DLSIM_E_ARG, "null weights array");
+  long long tensors = 0, out_tensors = 0;
+  size_t wo = 0;
+  for (int k = 0; k < b; ++k) {
+    const int n = fan_in[k];
+    if (n < 1) return fail(DLSIM_E_ARG, "task %d: n must be >= 1 (got %d)", k, n);
+    if (n > max) return fail(DLSIM_E_ARG, "task %d: n must be <= %d (got %d): %s", k, max, n, reason);
+    if (n_tensors[k] < 0) return fail(DLSIM_E_ARG, "task %d: n_tensors must be >= 0 (got %d)", k, n_tensors[k]);
+    if (!d2[k]) return fail(DLSIM_E_ARG, "task %d: null distance vector pointer", k);
+    if (dtype != DLSIM_F64)
+      for (int i = 0; i < n; ++i)
+        if (!(static_cast<double>(static_cast<float>(w[wo + i])) == w[wo + i]))
+          return fail(DLSIM_E_ARG, "task %d: weight %d (%.17g) is not representable in fp32", k, i, w[wo + i]);
+    wo += static_cast<size_t>(n);
+    tensors += n_tensors[k];
+    if (outs[k]) out_tensors += n_tensors[k];
+  }
+  if (tensors > 0 && (!in || !n_elems || (out_tensors > 0 && !out_off)))
+    return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  struct Wr {  // a range the call writes: task's vector (tensor < 0) or one tensor's output
+    uintptr_t a, b;
+    int task, tensor;
+  };
+  const auto name = [](const Wr& x) {
+    char buf[96];
+    if (x.tensor < 0) std::snprintf(buf, sizeof(buf), "the distance vector of task %d", x.task);
+    else std::snprintf(buf, sizeof(buf), "the output of task %d, tensor %d", x.task, x.tensor);
+    return std::string(buf);
+  };
+  std::vector<Wr> wr;
+  size_t lo = 0;
+  for (int k = 0; k < b; ++k) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d2[k]);
+    wr.push_back({a, a + sizeof(double) * static_cast<size_t>(fan_in[k]), k, -1});
+    for (int j = 0; j < n_tensors[k]; ++j) {
+      const size_t bytes = n_elems[lo + j] * esz;
+      if (!outs[k] || bytes == 0) continue;  // nothing stored
+      const uintptr_t o = reinterpret_cast<uintptr_t>(outs[k]) + out_off[lo + j];
+      wr.push_back({o, o + bytes, k, j});
+    }
+    lo += static_cast<size_t>(n_tensors[k]);
+  }
+  std::sort(wr.begin(), wr.end(), [](const Wr& x, const Wr& y) { return x.a < y.a; });
+  for (size_t k = 1; k < wr.size(); ++k)
+    if (wr[k].a < wr[k - 1].b)  // sorted by start and disjoint so far: the ends are sorted too
+      return fail(DLSIM_E_ARG, "%s overlaps %s", name(wr[k - 1]).c_str(), name(wr[k]).c_str());
+  size_t po = 0;
+  lo = 0;
+  for (int k = 0; k < b; ++k) {
+    const int n = fan_in[k], t = n_tensors[k];
+    for (int j = 0; j < t; ++j) {
+      const size_t bytes = n_elems[lo + j] * esz;
+      if (bytes == 0) continue;  // never read: any pointer will do
+      for (int i = 0; i < n; ++i) {
+        const void* p = in[po + static_cast<size_t>(i) * t + j];
+        if (!p) return fail(DLSIM_E_ARG, "task %d, tensor %d: null input pointer at index %d", k, j, i);
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
+        auto it = std::upper_bound(wr.begin(), wr.end(), a0, [](uintptr_t v, const Wr& x) { return v < x.b; });
+        if (it != wr.end() && it->a < a1)
+          return fail(DLSIM_E_ARG, "task %d, tensor %d: %s overlaps input %d", k, j, name(*it).c_str(), i);
       }
     }
     po += static_cast<size_t>(n) * static_cast<size_t>(t);

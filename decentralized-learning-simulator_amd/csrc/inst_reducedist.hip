@@ -8,15 +8,7 @@
 
 namespace dlsim_host __attribute__((visibility("hidden"))) {
 
-namespace {
-
-struct RdGeom {
-  int cap;          // compile-time row capacity: 4, 8, 16 or 32
-  size_t tile;      // elements a block takes per step
-  unsigned blocks;  // grid
-};
-
-// vec: every base is 16-byte aligned
+// vec: every base is 16-byte aligned (partials.hpp: a segment of a batched launch takes it too)
 RdGeom rd_geometry(int n, int elem_bytes, size_t nelem, bool vec) {
   RdGeom g;
   g.cap = n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
@@ -25,6 +17,8 @@ RdGeom rd_geometry(int n, int elem_bytes, size_t nelem, bool vec) {
   g.blocks = static_cast<unsigned>(std::min<size_t>(kDistGridBlocks, std::max<size_t>(tiles, 1)));
   return g;
 }
+
+namespace {
 
 template <class Op, bool VEC, class S>
 void rd_launch_main(const RdGeom& g, const S& s, int n, void* out, size_t nelem, double* ws, hipStream_t st) {
@@ -57,7 +51,7 @@ hipError_t rd_run(const void* const* in, int n, const double* w, void* out, size
       else rd_launch_main<Op, false>(g, s, n, outp, len, ws, st);
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(dlsim::k_reducedist_finish, dim3(finish_blocks(n)), dim3(dlsim::kBlock), 0, st,
+      hipLaunchKernelGGL(dlsim::k_reducedist_finish<>, dim3(finish_blocks(n)), dim3(dlsim::kBlock), 0, st,
                          static_cast<const double*>(ws), g.blocks, n, d2, (accumulate || o > 0) ? 1 : 0);
       return hipGetLastError();
     });

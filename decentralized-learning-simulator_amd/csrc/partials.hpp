@@ -1,8 +1,9 @@
 // partials.hpp — what the host dispatches of the n <= 32 input families share (inst_robust.hip,
-// inst_pairdist.hip, inst_pairdist_batch.hip, inst_reducedist.hip): the split of a long input into
+// inst_pairdist.hip, inst_pairdist_batch.hip, inst_reducedist.hip, inst_reducedist_batch.hip): the split of a long input into
 // launches of 32-bit byte offsets, the distance families' grid cap, partial-sum workspace and finish
-// grid, and the grid of one pairwise-distance call (PdGeom), which the flat entry and every segment of
-// a batched launch take from the same pd_geometry. Host code only.
+// grid, and the grid of one pairwise-distance call (PdGeom) and of one reduce-and-measure call
+// (RdGeom), which the flat entry and every segment of a batched launch take from the same pd_geometry
+// and rd_geometry. Host code only.
 #pragma once
 
 #include "dispatch.hpp"
@@ -50,6 +51,16 @@ struct PdGeom {
 };
 // elems16: elements of a 16-byte vector; vec: every base is 16-byte aligned
 PdGeom pd_geometry(int n, int elems16, size_t nelem, bool vec);
+
+// The grid of one reduce-and-measure call (inst_reducedist.hip defines rd_geometry; a segment of a
+// batched launch takes the same one, inst_reducedist_batch.hip).
+struct RdGeom {
+  int cap;          // compile-time row capacity: 4, 8, 16 or 32
+  size_t tile;      // elements a block takes per step
+  unsigned blocks;  // grid
+};
+// vec: every base is 16-byte aligned
+RdGeom rd_geometry(int n, int elem_bytes, size_t nelem, bool vec);
 
 inline unsigned finish_blocks(int items) {  // grid of a finish kernel: one wave per item (a pair, an input)
   return static_cast<unsigned>((items + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));

@@ -66,11 +66,15 @@ struct RdF16 {
   using Fold = F16Exact;
 };
 
-// Pointers and weights travel in the kernarg segment (scalar loads).
+// Pointers and weights travel in the kernarg segment (scalar loads). rd_tile
+// reads them through ptr(i) / wt(i), so that a segment of a batched launch
+// (RdTaskArgs, reducedist_batch_kernels.hpp) can stand in for the flat call's.
 template <class W>
 struct RdSlots {
   const void* p[kRdMaxInputs];
   W w[kRdMaxInputs];
+  __device__ const void* ptr(int i) const { return p[i]; }
+  __device__ W wt(int i) const { return w[i]; }
 };
 
 // bytes a lane takes of one row per tile on the vector path
@@ -130,7 +134,7 @@ __device__ __forceinline__ void rd_tile(const S& s, int n, void* __restrict__ ou
 #pragma unroll
     for (int i = 0; i < CAP; ++i) {
       r[i] = u32x4{0u, 0u, 0u, 0u};
-      if (i < n && live) r[i] = rd_ld<WB>(s.p[i], idx);
+      if (i < n && live) r[i] = rd_ld<WB>(s.ptr(i), idx);
     }
 #pragma unroll
     for (int i = 0; i < CAP; ++i) {
@@ -143,7 +147,7 @@ __device__ __forceinline__ void rd_tile(const S& s, int n, void* __restrict__ ou
 #pragma unroll
     for (int i = 0; i < CAP; ++i) {
       x[i][0] = 0;
-      if (i < n && live) x[i][0] = load_elem<F>(s.p[i], idx);
+      if (i < n && live) x[i][0] = load_elem<F>(s.ptr(i), idx);
     }
   }
   T a[EV];
@@ -153,10 +157,10 @@ __device__ __forceinline__ void rd_tile(const S& s, int n, void* __restrict__ ou
   for (int i = 0; i < CAP; ++i)
     if (i < n) {
       if constexpr (EV == 1) {
-        a[0] = F::step(a[0], s.w[i], x[i][0]);
+        a[0] = F::step(a[0], s.wt(i), x[i][0]);
       } else {
 #pragma unroll
-        for (int e = 0; e < EV; e += 2) F::step2(a[e], a[e + 1], s.w[i], x[i][e], x[i][e + 1]);
+        for (int e = 0; e < EV; e += 2) F::step2(a[e], a[e + 1], s.wt(i), x[i][e], x[i][e + 1]);
       }
     }
   if (live) {
@@ -185,25 +189,21 @@ __device__ __forceinline__ void rd_tile(const S& s, int n, void* __restrict__ ou
   }
 }
 
-// grid (blocks): block b takes the full tiles b, b + blocks, ..., the partial
-// tile goes to block (full tiles) mod blocks and the elements past the last
-// whole item to the last block; every block stores its CAP partial sums to
-// ws[i * blocks + b] (zeros where it had no tile, or for rows i >= n).
-// out == nullptr: distances only.
-template <class Op, int CAP, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_reducedist(const RdSlots<wt_t<typename Op::Fold>> s, int n,
-                                                       void* __restrict__ out, size_t nelem,
-                                                       double* __restrict__ ws) {
-  static_assert(kBlock == 256, "four waves: the block-end sum names them");
+// Block b of nblk: it takes the full tiles b, b + nblk, ..., the partial tile
+// goes to block (full tiles) mod nblk and the elements past the last whole
+// item to the last block; every block stores its CAP partial sums to
+// ws[i * nblk + b] (zeros where it had no tile, or for rows i >= n).
+// out == nullptr: distances only. red: kBlock / 64 rows of kPdSlots.
+template <class Op, int CAP, bool VEC, class S>
+__device__ __forceinline__ void rd_block(const S& s, int n, void* __restrict__ out, size_t nelem,
+                                         double* __restrict__ ws, size_t nblk, size_t b, double (*red)[kPdSlots]) {
   using F = typename Op::Fold;
   constexpr int EV = VEC ? rd_width<Op, CAP>() / F::kBytes : 1;
-  __shared__ double red[kBlock / 64][kPdSlots];
   double acc[CAP];
 #pragma unroll
   for (int k = 0; k < CAP; ++k) acc[k] = 0.0;
   const size_t items = nelem / EV;  // whole vectors, or elements
   const size_t full = items / kBlock;
-  const size_t nblk = gridDim.x, b = blockIdx.x;
   for (size_t t = b; t < full; t += nblk)
     rd_tile<Op, CAP, VEC, false>(s, n, out, t * kBlock + threadIdx.x, items, acc);
   if (full * kBlock < items && full % nblk == b)
@@ -215,15 +215,31 @@ __global__ __launch_bounds__(kBlock) void k_reducedist(const RdSlots<wt_t<typena
   pd_block_sum<CAP>(acc, ws, red, nblk, b);
 }
 
+// grid (blocks): rd_block over the launch's own grid.
+template <class Op, int CAP, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_reducedist(const RdSlots<wt_t<typename Op::Fold>> s, int n,
+                                                       void* __restrict__ out, size_t nelem,
+                                                       double* __restrict__ ws) {
+  static_assert(kBlock == 256, "four waves: the block-end sum names them");
+  __shared__ double red[kBlock / 64][kPdSlots];
+  rd_block<Op, CAP, VEC>(s, n, out, nelem, ws, gridDim.x, blockIdx.x, red);
+}
+
 // One wave per input: its partials of all blocks in pairdist's finish order.
-// accumulate: the sum is added to what d2[i] holds.
+// accumulate: the sum is added to what d2[i] holds, with pd_add_held (the sum
+// first, the held value second: the operands `d2[i] + v` compiled to here
+// before the batched kernels came, profiles/geomed_batch/finish_add_operands.md),
+// so that this kernel and k_reducedist_batch_finish agree on NaN payloads too.
+// (A template so that the header, included by two units, defines it once:
+// launched as k_reducedist_finish<>.)
+template <class = void>
 __global__ __launch_bounds__(kBlock) void k_reducedist_finish(const double* __restrict__ ws, unsigned blocks, int n,
                                                               double* __restrict__ d2, int accumulate) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (i >= n) return;
   const double v = pd_finish_sum(ws + static_cast<size_t>(i) * blocks, blocks, lane);
-  if (lane == 0) d2[i] = accumulate ? d2[i] + v : v;
+  if (lane == 0) d2[i] = accumulate ? pd_add_held(v, d2[i]) : v;
 }
 
 }  // namespace dlsim

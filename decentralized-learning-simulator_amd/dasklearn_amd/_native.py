@@ -72,6 +72,8 @@ EXPORTS = (
     "dlsim_pairdist_geometry",
     "dlsim_pairwise_sqdist_batched",
     "dlsim_pairdist_batch_geometry",
+    "dlsim_wreduce_dist_batched",
+    "dlsim_reducedist_batch_geometry",
     "dlsim_wreduce_dist",
     "dlsim_wreduce_dist_tensors",
     "dlsim_reducedist_geometry",
@@ -249,6 +251,12 @@ def load() -> ctypes.CDLL:
         lib.dlsim_wreduce_dist_tensors.restype = i
         lib.dlsim_reducedist_geometry.argtypes = [i, i, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint)]
         lib.dlsim_reducedist_geometry.restype = i
+        lib.dlsim_wreduce_dist_batched.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(vp),
+                                                   ctypes.POINTER(sz), ctypes.POINTER(sz), dp, ctypes.POINTER(vp), i,
+                                                   ctypes.POINTER(vp), i, vp]
+        lib.dlsim_wreduce_dist_batched.restype = i
+        lib.dlsim_reducedist_batch_geometry.argtypes = [i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
+        lib.dlsim_reducedist_batch_geometry.restype = i
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -799,6 +807,67 @@ def reducedist_geometry(n: int, torch_dtype, numel: int):
     """(tile elements, blocks) of dlsim_wreduce_dist for n 16-byte-aligned
     inputs of numel elements (dlsim_reducedist_geometry; no GPU needed)."""
     return _geometry("dlsim_reducedist_geometry", n, torch_dtype, numel)
+
+
+def wreduce_dist_batched_raw(fan_in: Sequence[int], n_tensors: Sequence[int], in_ptrs: Sequence[int],
+                             numels: Sequence[int], out_offsets: Sequence[int], weights: Sequence[float],
+                             out_bases: Sequence[Optional[int]], dtype: int, d2_ptrs: Sequence[int],
+                             accumulate: bool, stream_handle) -> None:
+    """dlsim_wreduce_dist_batched on pointers the caller has already
+    validated: task k's fan_in[k] * n_tensors[k] pointers (model-major),
+    n_tensors[k] lengths and output offsets and fan_in[k] weights follow task
+    k-1's; out_bases[k] may be None (distances only); fan_in[k] doubles at
+    d2_ptrs[k]."""
+    _check("dlsim_wreduce_dist_batched",
+           load().dlsim_wreduce_dist_batched(len(fan_in), _int_array(fan_in), _int_array(n_tensors),
+                                             _ptr_array(in_ptrs), _size_array(numels), _size_array(out_offsets),
+                                             _double_array(weights), _ptr_array(out_bases), dtype,
+                                             _ptr_array(d2_ptrs), int(bool(accumulate)), stream_handle))
+
+
+def wreduce_dist_batched(tasks, accumulate: bool = False, stream=None):
+    """dlsim_wreduce_dist_batched: tasks = [(inputs, weights, out, d2)], each
+    as wreduce_dist takes them (its exceptions too), all of one dtype on one
+    device; every output and vector in a few shared launches, bit-identical
+    to one wreduce_dist call each. `out` may be None. No output or vector may
+    share memory with an input of any task or with another output or vector;
+    inputs may be shared. Stream-ordered. Returns [(out, d2)]."""
+    if not tasks:
+        return []
+    dev, dt0 = tasks[0][3].device, None
+    fan, ptrs, numels, ws, outs, d2s = [], [], [], [], [], []
+    for inputs, weights, out, d2 in tasks:
+        n = len(inputs)
+        if n < 1:
+            raise IndexError("list index out of range")
+        check_reducedist_fan_in(n)
+        assert len(weights) == n
+        _check_distances(d2, n, "vector")
+        dt, numel = _check_flat_inputs(inputs, out, dev, "reduce-and-measure")
+        if d2.device != dev:
+            raise ValueError("reduce-and-measure needs device tensors on one device (no CPU path)")
+        if dt0 is not None and dt != dt0:
+            raise ValueError("one batched call takes tasks of one dtype")
+        dt0 = dt
+        fan.append(n)
+        ptrs += [t.data_ptr() for t in inputs]
+        numels.append(numel)
+        ws += [float(w) for w in weights]
+        outs.append(None if out is None else out.data_ptr())
+        d2s.append(d2.data_ptr())
+    wreduce_dist_batched_raw(fan, [1] * len(fan), ptrs, numels, [0] * len(fan), ws, outs,
+                             dtype_code(dt0, single_task=True), d2s, accumulate, _stream_handle(dev, stream))
+    return [(t[2], t[3]) for t in tasks]
+
+
+def reducedist_batch_geometry(n: int, torch_dtype):
+    """(max_segments, max_ptrs) of dlsim_reducedist_batch_geometry: the limits
+    of one launch of the batched reduce-and-measure kernel (no GPU needed)."""
+    ms, mp = ctypes.c_int(0), ctypes.c_int(0)
+    _check("dlsim_reducedist_batch_geometry",
+           load().dlsim_reducedist_batch_geometry(int(n), dtype_code(torch_dtype, single_task=True), ctypes.byref(ms),
+                                                  ctypes.byref(mp)))
+    return ms.value, mp.value
 
 
 DLSIM_ALLOC_CONTIGUOUS = 1

@@ -55,16 +55,24 @@ whose parameter list differs from models[0]'s, ValueError; so do bad nu, T, tau
 or L.
 
 Cost: the weights need the distances on the host, so every pass pays one D2H
-copy of n doubles and one stream synchronisation.
+copy of n doubles and one stream synchronisation. The aggregates of one
+simulated round (`RoundExecutor`, `aggregate_batch`) share them: the tasks go
+in lockstep, every pass of every task in batched launches
+(csrc/reducedist_batch_kernels.hpp) with one D2H copy and one
+synchronisation per device and pass (`model_inputs.geomed_arena_tasks`).
+`consensus_distance_batch` is pass 0 on its own.
 """
 import math
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
+import torch
 from torch import nn
 
 from dasklearn_amd import _native
 from dasklearn_amd.gradient_aggregation import GradientAggregation
-from dasklearn_amd.model_inputs import ReduceDistPlan, fp32_rounded, reduce_with_distances
+from dasklearn_amd.model_inputs import (ReduceDistPlan, fp32_rounded, reduce_dist_arena_tasks, reduce_with_distances,
+                                        vectors_to_host)
+from dasklearn_amd.wave_tasks import finish_modules
 
 aggregate_with_distances = reduce_with_distances  # public here, as krum.model_distances
 
@@ -84,6 +92,34 @@ def consensus_distance(models: List[nn.Module], weights: Optional[Sequence[float
     float64 tensor of every model's squared distance to it; the consensus
     distance of the D-PSGD literature is sum_i alpha_i * d2[i]."""
     return reduce_with_distances(models, _alphas(models, weights))
+
+
+def consensus_distance_batch(tasks: Sequence[Tuple[List[nn.Module], Optional[Sequence[float]]]]):
+    """consensus_distance for every (models, weights) of `tasks` (every
+    neighbourhood of a round) in one call: [(mean_module, d2)], each
+    bit-identical to consensus_distance(models, weights), its exceptions too.
+    The device-resident tasks share batched launches, one D2H copy and one
+    stream synchronisation per device (model_inputs.reduce_dist_arena_tasks);
+    a task with a host model, a model on another device or a non-contiguous
+    parameter goes through consensus_distance."""
+    from dasklearn_amd.gradient_aggregation.krum import _resident_entry
+    results = [None] * len(tasks)
+    prepared, where, ws = [], [], []
+    for ti, (models, weights) in enumerate(tasks):
+        alphas = _alphas(models, weights)
+        _native.check_reducedist_fan_in(len(models))
+        entry = _resident_entry(models, None)
+        if entry is None:
+            results[ti] = reduce_with_distances(models, alphas)
+            continue
+        prepared.append(entry)
+        where.append(ti)
+        ws.append(fp32_rounded(alphas))
+    outs, slots, bufs = reduce_dist_arena_tasks(prepared, [range(len(w)) for w in ws], ws)
+    d2s = vectors_to_host(slots, bufs)  # waits for the stream
+    for ti, mod, d2 in zip(where, finish_modules(prepared, outs), d2s):
+        results[ti] = (mod, torch.tensor(d2, dtype=torch.float64))
+    return results
 
 
 def weiszfeld_weights(d2: Sequence[float], alphas: Sequence[float], nu: float) -> Optional[List[float]]:

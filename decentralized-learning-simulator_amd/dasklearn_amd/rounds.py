@@ -20,9 +20,9 @@ anything else (host models, other devices) is copied once into a fresh arena
 aggregate chain never crosses PCIe when the train function works on the
 device. Results are bit-identical to running the same tasks one by one with
 functions.aggregate under the same settings.gradient_aggregation: FedAvg, the
-median, the trimmed mean, Krum and Multi-Krum in batched launches, the other
-methods through their plugin task by task (batch.method_route decides; a
-task travels as a wave_tasks.ArenaTask).
+median, the trimmed mean, Krum and Multi-Krum, the geometric median and
+centered clipping in batched launches, any other plugin task by task
+(batch.method_route decides; a task travels as a wave_tasks.ArenaTask).
 """
 from __future__ import annotations
 
@@ -35,9 +35,9 @@ from torch import nn
 from . import _native
 from .arena import (ParamLayout, ZipMismatch, _target_device, aggregate_modules, aligned_empty, arena_empty, base_align,
                     layout_of, module_params, registered_arenas, row_stride)
-from .batch import PLUGIN, _resolve, method_route
+from .batch import GEOMED, PLUGIN, _resolve, method_route
 from .gradient_aggregation import GradientAggregationMethod
-from .model_inputs import krum_arena_tasks, robust_arena_tasks
+from .model_inputs import geomed_arena_tasks, krum_arena_tasks, robust_arena_tasks
 from .model_manager import ModelManager
 from .wave_tasks import ArenaTask, _device_views, aggregate_arena_tasks
 
@@ -276,11 +276,14 @@ class RoundExecutor:
         for bit to functions.aggregate per task (ModelManager's plugins), in
         the batched launches batch.method_route picks: FedAvg; MEDIAN and
         TRIMMED_MEAN; KRUM and MULTI_KRUM when ModelManager's plugin is a Krum
-        or MultiKrum class (f and m read from the class). Every task is checked
+        or MultiKrum class (f and m read from the class); GEOMETRIC_MEDIAN and
+        CENTERED_CLIP when it is a GeometricMedian or CenteredClip class
+        (iterations, nu and tau read from the class; the tasks keep their
+        weights). Every task is checked
         first and raises what its plugin raises; then the wave's models are
         resolved (one upload of the host models, arenas and separate device
         tensors read in place) and every task runs in one batched call per
-        dtype. The other methods and any other plugin (and an unknown value,
+        dtype. Any other plugin (and an unknown value,
         which fails as the per-task path fails) call the plugin per task on
         the resolved models and keep the result on the device. on_launched:
         see wave_tasks.finish_modules (the executor releases the results no
@@ -298,8 +301,11 @@ class RoundExecutor:
         route = method_route(method, self.settings, lambda _, s: ModelManager(None, s, 0).get_aggregation_method())
         if route.kind == PLUGIN:
             return route.per_task(resolved)
-        for models, weights in resolved:
-            route.check(models, weights)
+        keeps = fedavg or route.kind == GEOMED  # the kinds whose tasks carry weights
+        for j, (models, weights) in enumerate(resolved):
+            alphas = route.check(models, weights)
+            if route.kind == GEOMED:
+                resolved[j] = (models, alphas)
         cache: dict = {}
         walked: dict = {}
         self._upload_host_models([m for models, _ in resolved for m in models], cache, walked)
@@ -307,7 +313,7 @@ class RoundExecutor:
         single = {}  # task position -> result of the per-parameter zip path
         for j, (models, ws) in enumerate(resolved):
             try:
-                prepared.append(self._wave_task(models, ws if fedavg else None, cache, walked))
+                prepared.append(self._wave_task(models, ws if keeps else None, cache, walked))
             except ZipMismatch:  # parameter lists differ: FedAvg zips (fedavg.py:23-24), the others raise it
                 if not fedavg:
                     raise
@@ -318,7 +324,7 @@ class RoundExecutor:
         walked.clear()
         # the launch functions as this module names them: a probe that times one replaces it here
         outs = route.run(prepared, on_launched, self.mode,
-                         (aggregate_arena_tasks, robust_arena_tasks, krum_arena_tasks))
+                         (aggregate_arena_tasks, robust_arena_tasks, krum_arena_tasks, geomed_arena_tasks))
         if not single:
             return outs
         it = iter(outs)

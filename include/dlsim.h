@@ -948,6 +948,69 @@ int dlsim_wreduce_dist_tensors(const void* const* d_inputs, int n, int t, const 
 int dlsim_reducedist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
 
 /*
+ * dlsim_wreduce_dist_batched: b independent dlsim_wreduce_dist_tensors tasks
+ * in a few launches (one pass of the geometric median or of centered clipping
+ * for every peer of a simulated round). The reduce-and-measure
+ * counterpart of dlsim_pairwise_sqdist_batched, whose array conventions it
+ * keeps. (New: it replaces no reference code.)
+ *   fan_in         host array of b fan-ins, 1 <= fan_in[k] <= 32
+ *   n_tensors      host array of b tensor counts, >= 0
+ *   d_inputs       host array of sum(fan_in[k] * n_tensors[k]) device pointers:
+ *                  task k's, model-major (tensor j of model i at
+ *                  i*n_tensors[k] + j), follow task k-1's
+ *   n_elems        host array of sum(n_tensors) element counts: task k's follow
+ *                  task k-1's
+ *   out_off_bytes  host array of sum(n_tensors) byte offsets into d_out[k], laid
+ *                  out as n_elems (unused where d_out[k] is null)
+ *   h_weights      host array of sum(fan_in) doubles, task by task; the weight
+ *                  rule of dlsim_wreduce_dist holds for each
+ *   d_out          host array of b device pointers; d_out[k] may be null: task k
+ *                  produces distances only
+ *   d_d2           host array of b device pointers; task k writes fan_in[k]
+ *                  doubles
+ *   accumulate     0 or 1, for every task, as dlsim_wreduce_dist
+ * Task k's output and vector hold the bits that
+ *   dlsim_wreduce_dist_tensors(inputs_k, fan_in[k], n_tensors[k], n_elems_k,
+ *                              out_off_k, weights_k, d_out[k], dtype, d_d2[k],
+ *                              accumulate, stream)
+ * gives, for all four dtypes and any alignment: every non-empty tensor is a
+ * segment with the grid, the tiles, the stores and the block partials of its
+ * own flat call, and a vector's segments are added in tensor order. A task
+ * without an element (n_tensors[k] == 0, or every length 0) writes zeros, or
+ * nothing when accumulating; b == 0 is a no-op. The tasks are regrouped by the
+ * kernel's capacity (fan-in up to 4, 8, 16, 32) and run in launches of at most
+ * DLSIM_REDUCEDIST_BATCH_MAX_SEGMENTS segments and the row pointers that
+ * dlsim_reducedist_batch_geometry reports, vector-form segments (every input
+ * base 16-byte aligned, the output base aligned or null) and element-form ones
+ * in launches of their own; a task with a tensor past one launch's byte limit
+ * (2 GiB - 1 MiB) runs as dlsim_wreduce_dist_tensors runs it, and so does a
+ * call with b == 1 (the bits are the same either way). One stream-ordered
+ * workspace (hipMallocAsync / hipFreeAsync on `stream`) holds the partials of
+ * the whole call.
+ * Inputs may alias each other within and across tasks (in a ring one model is
+ * a row of several tasks). An output range or a vector may share no byte with
+ * an input of any task, nor with another output range or vector. Argument
+ * errors (DLSIM_E_ARG: a null array or pointer, b < 0, a fan-in outside 1..32,
+ * n_tensors < 0, a weight not representable, accumulate not 0 or 1, the
+ * overlaps above; DLSIM_E_DTYPE) are decided for the whole list before the
+ * first launch and before any HIP call. Stream-ordered; no synchronisation.
+ */
+#define DLSIM_REDUCEDIST_BATCH_MAX_SEGMENTS 32
+int dlsim_wreduce_dist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* d_inputs,
+                               const size_t* n_elems, const size_t* out_off_bytes, const double* h_weights,
+                               void* const* d_out, int dtype, double* const* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_reducedist_batch_geometry: the limits of one launch of
+ * dlsim_wreduce_dist_batched for tasks of fan-in n and this dtype, for tests
+ * that aim past them (a segment's tile and grid are
+ * dlsim_reducedist_geometry's). The pointer limit depends on the weight type:
+ * 192 for the 2- and 4-byte dtypes (fp32 weights), 128 for DLSIM_F64. Host
+ * only. (New: no reference counterpart.)
+ */
+int dlsim_reducedist_batch_geometry(int n, int dtype, int* max_segments, int* max_ptrs);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
