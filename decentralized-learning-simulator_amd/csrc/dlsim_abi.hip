@@ -314,6 +314,8 @@ hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, 
 hipError_t robust_batched(int b, const int* fan_in, const void* const* in, const int* lo, const int* hi,
                           void* const* outs, const size_t* nelem, int dtype, hipStream_t st);
 size_t robust_batch_tile_elems(int n, int dtype);
+hipError_t robust_nearest_flat(const void* const* in, int n, int keep, void* out, size_t nelem, int dtype,
+                               hipStream_t st);
 hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
                          hipStream_t st);
 void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
@@ -336,6 +338,13 @@ constexpr const char* kReducedistLimit = "the inputs' rows and accumulators are 
 int check_robust_window(int n, int lo, int hi) {
   if (!(0 <= lo && lo < hi && hi <= n))
     return fail(DLSIM_E_ARG, "the window must satisfy 0 <= lo < hi <= n (got lo %d, hi %d, n %d)", lo, hi, n);
+  return DLSIM_OK;
+}
+
+// the kept count of dlsim_robust_nearest_reduce / _tensors
+int check_nearest_keep(int n, int keep) {
+  if (!(1 <= keep && keep <= n))
+    return fail(DLSIM_E_ARG, "keep must satisfy 1 <= keep <= n (got keep %d, n %d)", keep, n);
   return DLSIM_OK;
 }
 
@@ -1239,6 +1248,45 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
     const hipError_t e =
         robust_flat(row, n, lo, hi, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
     if (e != hipSuccess) return hip_fail(e, "robust reduce launch");
+  }
+  return DLSIM_OK;
+}
+
+int dlsim_robust_nearest_reduce(const void* const* d_inputs, int n, int keep, void* d_out, size_t n_elems, int dtype,
+                                void* stream) {
+  g_err.clear();
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_INPUTS, dtype, kRobustLimit);
+  if (rc == DLSIM_OK) rc = check_nearest_keep(n, keep);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
+  if (n_elems == 0) return DLSIM_OK;
+  if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+  // any shared byte is rejected, as dlsim_robust_reduce
+  const size_t bytes = n_elems * elem_bytes(dtype);
+  rc = check_inputs_apart(d_inputs, 1, n, bytes, addr(d_out), addr(d_out) + bytes, "output");
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = robust_nearest_flat(d_inputs, n, keep, d_out, n_elems, dtype, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "robust nearest reduce launch");
+}
+
+int dlsim_robust_nearest_reduce_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                        const size_t* out_off_bytes, int keep, void* d_out, int dtype, void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_INPUTS, dtype, kRobustLimit);
+  if (rc == DLSIM_OK) rc = check_nearest_keep(n, keep);
+  if (rc != DLSIM_OK || t == 0) return rc;
+  if (!d_inputs || !n_elems || !out_off_bytes) return fail(DLSIM_E_ARG, "null array argument");
+  rc = check_tensor_outputs(d_inputs, n, t, n_elems, d_out, out_off_bytes, elem_bytes(dtype));
+  if (rc != DLSIM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const void* row[DLSIM_MAX_ROBUST_INPUTS];
+  for (int k = 0; k < t; ++k) {
+    if (n_elems[k] == 0) continue;
+    gather_row(d_inputs, n, t, k, row);
+    const hipError_t e =
+        robust_nearest_flat(row, n, keep, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
+    if (e != hipSuccess) return hip_fail(e, "robust nearest reduce launch");
   }
   return DLSIM_OK;
 }

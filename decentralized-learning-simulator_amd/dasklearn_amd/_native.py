@@ -67,6 +67,8 @@ EXPORTS = (
     "dlsim_robust_reduce_batched",
     "dlsim_robust_batch_geometry",
     "dlsim_robust_reduce_tensors_batched",
+    "dlsim_robust_nearest_reduce",
+    "dlsim_robust_nearest_reduce_tensors",
     "dlsim_pairwise_sqdist",
     "dlsim_pairwise_sqdist_tensors",
     "dlsim_pairdist_geometry",
@@ -232,6 +234,11 @@ def load() -> ctypes.CDLL:
         lib.dlsim_robust_batch_geometry.restype = i
         lib.dlsim_robust_reduce_tensors_batched.argtypes = lib.dlsim_robust_reduce_tensors.argtypes
         lib.dlsim_robust_reduce_tensors_batched.restype = i
+        lib.dlsim_robust_nearest_reduce.argtypes = [ctypes.POINTER(vp), i, i, vp, sz, i, vp]
+        lib.dlsim_robust_nearest_reduce.restype = i
+        lib.dlsim_robust_nearest_reduce_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz),
+                                                            ctypes.POINTER(sz), i, vp, i, vp]
+        lib.dlsim_robust_nearest_reduce_tensors.restype = i
         lib.dlsim_pairwise_sqdist.argtypes = [ctypes.POINTER(vp), i, sz, i, vp, i, vp]
         lib.dlsim_pairwise_sqdist.restype = i
         lib.dlsim_pairwise_sqdist_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), i, vp, i, vp]
@@ -621,6 +628,34 @@ def robust_reduce_tensors_batched_raw(in_ptrs: Sequence[int], n: int, numels: Se
     _check("dlsim_robust_reduce_tensors_batched",
            load().dlsim_robust_reduce_tensors_batched(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
                                                       _size_array(out_offsets), int(lo), int(hi), out_base, dtype,
+                                                      stream_handle))
+
+
+def robust_nearest_reduce(inputs, keep: int, out, stream=None):
+    """dlsim_robust_nearest_reduce: per element, the mean of the `keep` sorted
+    values closest to the lower median of the n inputs' values (ties to the
+    smaller side; include/dlsim.h has the rule), summed in ascending order.
+    Tensors, exceptions and stream order as robust_reduce."""
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_robust_fan_in(n)
+    dt, numel = _check_flat_inputs(inputs, out, out.device, "robust nearest reduce")
+    _check("dlsim_robust_nearest_reduce",
+           load().dlsim_robust_nearest_reduce(_ptr_array([t.data_ptr() for t in inputs]), n, int(keep),
+                                              out.data_ptr(), numel, dtype_code(dt, single_task=True),
+                                              _stream_handle(out.device, stream)))
+    return out
+
+
+def robust_nearest_reduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int],
+                                      out_offsets: Sequence[int], keep: int, out_base: int, dtype: int,
+                                      stream_handle) -> None:
+    """dlsim_robust_nearest_reduce_tensors, as robust_reduce_tensors_raw."""
+    check_robust_fan_in(n)
+    _check("dlsim_robust_nearest_reduce_tensors",
+           load().dlsim_robust_nearest_reduce_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
+                                                      _size_array(out_offsets), int(keep), out_base, dtype,
                                                       stream_handle))
 
 

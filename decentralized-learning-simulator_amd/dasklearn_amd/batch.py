@@ -39,12 +39,17 @@ def _resolve(models, weights) -> List[float]:
 def method_window(method, settings):
     """lo_hi_fn (fan-in -> window [lo, hi)) of a batched method: MEDIAN, or
     TRIMMED_MEAN with settings.aggregation_trim (default 1, as ModelManager);
-    None for every other method."""
+    None for every other method, and for TRIMMED_MEAN under
+    settings.aggregation_trim_rule = "median" (MeanAroundMedian has no window
+    per launch and no batched form: it runs as a plugin, per task)."""
     from .gradient_aggregation import GradientAggregationMethod as M
     from .gradient_aggregation.robust import median_window, trimmed_window
+    from .model_manager import trim_rule
     if method == M.MEDIAN:
         return median_window
     if method == M.TRIMMED_MEAN:
+        if trim_rule(settings) == "median":
+            return None
         trim = int(getattr(settings, "aggregation_trim", 1))
         if trim < 0:  # TrimmedMean.with_trim's check
             raise ValueError(f"trim must be >= 0 (got {trim})")
@@ -195,7 +200,8 @@ def method_route(method, settings, lookup=method_plugin) -> MethodRoute:
     """The one decision both dispatchers (aggregate_batch, RoundExecutor) make: FedAvg (None too) takes
     the FedAvg launches; else a method_window the order-statistic launches; else a Krum or MultiKrum
     plugin class (krum_rule) the Krum launches; else a GeometricMedian or CenteredClip class (geomed_rule)
-    the lockstep reduce-and-measure launches; else the plugin runs per task. lookup(method,
+    the lockstep reduce-and-measure launches; else the plugin runs per task (MeanAroundMedian and Bulyan,
+    the variants of TRIMMED_MEAN and MULTI_KRUM, among them: no batched form yet). lookup(method,
     settings): the plugin class, as the caller's per-task path finds it."""
     from .gradient_aggregation import GradientAggregationMethod
     if method is None or method == GradientAggregationMethod.FEDAVG:

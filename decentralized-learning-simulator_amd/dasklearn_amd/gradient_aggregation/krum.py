@@ -52,7 +52,7 @@ from dasklearn_amd import _native
 from dasklearn_amd.arena import _target_device, input_arenas
 from dasklearn_amd.gradient_aggregation import GradientAggregation
 from dasklearn_amd.gradient_aggregation.robust import _check_unweighted
-from dasklearn_amd.model_inputs import (distances_arena_tasks, krum_modules,  # noqa: F401
+from dasklearn_amd.model_inputs import (bulyan_modules, distances_arena_tasks, krum_modules,  # noqa: F401
                                         model_distances)  # (model_distances: public here)
 from dasklearn_amd.wave_tasks import ArenaTask
 
@@ -140,6 +140,48 @@ def krum_select(d2: Sequence[Sequence[float]], f: int, m: int = 1) -> List[int]:
     return sorted(sorted(range(n), key=lambda i: (scores[i], i))[:m])
 
 
+def check_bulyan_params(n: int, f: int) -> None:
+    """ValueError unless f >= 0 and n >= 4f + 3."""
+    if f < 0 or n < 4 * f + 3:
+        raise ValueError(f"Bulyan over n = {n} models with f = {f} Byzantine ones: needs f >= 0 and n >= 4*f + 3")
+
+
+def bulyan_select(d2: Sequence[Sequence[float]], f: int) -> List[int]:
+    """Bulyan's first stage on the n x n matrix d2 (any nested sequence of
+    floats): Krum run theta = n - 2f times, each time over the models that are
+    left. D as for Krum (a non-finite entry counts as +Inf). R = all indices;
+    theta times, with r = |R|:
+
+        score[i] = the k = min(r - 1, max(1, r - f - 2)) smallest D[i][j],
+                   j in R without i, added in ascending order (k = 0 for r = 1)
+        the minimum by (score, index) leaves R and is chosen
+
+    Returns the theta chosen indices in ascending order. While r >= 2f + 3, k
+    is Krum's r - f - 2. The paper does not say what Krum means below 2f + 3
+    remaining models, which the last rounds reach; clamping k into [1, r - 1]
+    (the nearest neighbour at least, never more neighbours than there are) is
+    this library's choice."""
+    n = len(d2)
+    f = int(f)
+    check_bulyan_params(n, f)
+    D = [[float(d2[i][j]) if math.isfinite(d2[i][j]) else math.inf for j in range(n)] for i in range(n)]
+    left = list(range(n))
+    chosen = []
+    for _ in range(n - 2 * f):
+        r = len(left)
+        k = min(r - 1, max(1, r - f - 2))
+        best = None
+        for i in left:
+            s = 0.0
+            for v in sorted(D[i][j] for j in left if j != i)[:k]:
+                s += v
+            if best is None or (s, i) < best:
+                best = (s, i)
+        left.remove(best[1])
+        chosen.append(best[1])
+    return sorted(chosen)
+
+
 class Krum(GradientAggregation):
     """The one model closest to its n - f - 2 nearest neighbours; f Byzantine
     peers are tolerated among n >= 2f + 3."""
@@ -192,3 +234,38 @@ class MultiKrum(GradientAggregation):
             if m < 1:
                 raise ValueError(f"m must be >= 1 (got {m})")
         return type(f"MultiKrum{f}" + ("" if m is None else f"x{m}"), (cls,), {"f": f, "m": m})
+
+
+class Bulyan(GradientAggregation):
+    """Bulyan (El Mhamdi et al., 2018): Krum's selection run theta = n - 2f
+    times (bulyan_select), then, per parameter element, the mean of the
+    theta - 2f values closest to the median of the selected models' values
+    (robust.MeanAroundMedian's rule and kernel). A distance-based selection
+    followed by a coordinate-wise rule: a peer that passes Krum with one
+    poisoned coordinate is caught by the second stage. f Byzantine peers are
+    tolerated among n >= 4f + 3. A variant of MULTI_KRUM
+    (`settings.aggregation_krum_rule = "bulyan"`).
+
+    The parameters equal MeanAroundMedian.aggregate(selected, keep=theta - 2f)
+    bit for bit, the selected models in ascending index order; buffers,
+    attributes and strides are copy.deepcopy(models[0])'s. Cost: as Multi-Krum,
+    one D2H copy of n*n doubles and one stream synchronisation; the second
+    stage reads the rows the distances read. The aggregates of a round run
+    task by task (no batched form yet)."""
+
+    f = 1
+
+    @classmethod
+    def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
+                  to_host: Optional[bool] = None) -> nn.Module:
+        _check_unweighted("Bulyan", models, weights)
+        return bulyan_modules(models, cls.f, to_host=to_host)
+
+    @classmethod
+    def with_params(cls, f: int):
+        """A Bulyan class for Byzantine count f: the plugin signature
+        ModelManager calls."""
+        f = int(f)
+        if f < 0:
+            raise ValueError(f"f must be >= 0 (got {f})")
+        return type(f"Bulyan{f}", (cls,), {"f": f})

@@ -23,13 +23,19 @@ models, or a model whose parameter list differs from models[0]'s, ValueError.
 The arithmetic runs in one HIP kernel per dtype group
 (csrc/robust_kernels.hpp: an in-register sorting network per element) through
 dasklearn_amd.model_inputs.robust_modules.
+
+MeanAroundMedian (MeaMed / Phocas, Xie et al., 2018; a variant of TRIMMED_MEAN:
+`settings.aggregation_trim_rule = "median"`) averages, per element, the `keep`
+sorted values closest to the lower median instead of a fixed rank window; its
+kernels (csrc/robust_nearest_kernels.hpp) choose the window per
+element, through dasklearn_amd.model_inputs.nearest_modules.
 """
 from typing import List, Optional
 
 from torch import nn
 
 from dasklearn_amd.gradient_aggregation import GradientAggregation
-from dasklearn_amd.model_inputs import robust_modules
+from dasklearn_amd.model_inputs import nearest_modules, robust_modules
 
 
 def _check_unweighted(name: str, models, weights) -> None:
@@ -97,3 +103,45 @@ class TrimmedMean(GradientAggregation):
         if trim < 0:
             raise ValueError(f"trim must be >= 0 (got {trim})")
         return type(f"TrimmedMean{trim}", (cls,), {"trim": trim})
+
+
+class MeanAroundMedian(GradientAggregation):
+    """The coordinate-wise mean around the median: per element, of the n sorted
+    values s the keep = n - 2*trim closest to the lower median p = s[(n-1)//2]
+    are averaged in ascending order. TrimmedMean drops `trim` values at each
+    end whatever they are; this drops the 2*trim values farthest from the
+    centre, on whichever side they lie.
+
+    The distance of s[j] is +0.0 where s[j] sorts equal to p (the same bits;
+    any two NaNs), else |s[j] - p| rounded once in fp32 (fp64 for fp64 models),
+    ranked 0 <= ... <= +Inf < NaN. The window starts at the median and grows
+    keep - 1 times, by the right neighbour iff there is one and the left
+    neighbour is missing or strictly farther: ties go left. keep = 1 is
+    CoordinateMedian, keep = n the trim-0 TrimmedMean, bit for bit. Up to
+    `trim` peers sending Inf or NaN leave the result finite."""
+
+    trim = 1
+
+    @classmethod
+    def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
+                  to_host: Optional[bool] = None, keep: Optional[int] = None) -> nn.Module:
+        """keep: the kept count itself (1 <= keep <= n) instead of
+        n - 2*trim."""
+        _check_unweighted("MeanAroundMedian", models, weights)
+        if keep is not None:
+            return nearest_modules(models, lambda n: keep, to_host=to_host)
+        b = cls.trim
+
+        def kept(n):
+            lo, hi = trimmed_window(n, b)
+            return hi - lo
+        return nearest_modules(models, kept, to_host=to_host)
+
+    @classmethod
+    def with_trim(cls, trim: int):
+        """A MeanAroundMedian class that keeps n - 2*trim values: the plugin
+        signature ModelManager calls."""
+        trim = int(trim)
+        if trim < 0:
+            raise ValueError(f"trim must be >= 0 (got {trim})")
+        return type(f"MeanAroundMedian{trim}", (cls,), {"trim": trim})

@@ -1,5 +1,6 @@
-"""The aggregates over n <= 32 models (median and trimmed mean; pairwise distances and Krum; the
-reduce-and-measure pass of the geometric median and centered clipping) and ModelInputs, which resolves
+"""The aggregates over n <= 32 models (median and trimmed mean; the mean around the median; pairwise
+distances, Krum and Bulyan; the reduce-and-measure pass of the geometric median and centered clipping) and
+ModelInputs, which resolves
 a list of models into what their kernels read. arena.py re-exports the public names. The batched forms
 (robust_arena_tasks, distances_arena_tasks, krum_arena_tasks, reduce_dist_arena_tasks, geomed_arena_tasks)
 take lists of wave_tasks.ArenaTask, whose module describes the record; batch.method_route picks among them."""
@@ -139,6 +140,75 @@ def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Opti
                                                           raw_stream)
         if not host_out and any(k is not None and len(k) for k in inputs.keep):
             torch.cuda.current_stream(dev).synchronize()  # the staged copies' sources may go now
+    return inputs.module(outs, to_host)
+
+
+def _nearest_outs(inputs: ModelInputs, idx: Sequence[int], keep: int, host_out: bool) -> Dict[torch.dtype, torch.Tensor]:
+    """One arena per dtype group of inputs.layout: the mean around the median
+    (dlsim_robust_nearest_reduce) with `keep` values over the models `idx` of
+    `inputs`, in that order, one call per non-empty group; the empty groups'
+    arenas on the host when host_out. Stream-ordered: nothing waits."""
+    layout, dev = inputs.layout, inputs.dev
+    idx = list(idx)
+    outs: Dict[torch.dtype, torch.Tensor] = {dt: torch.empty(0, dtype=dt, device="cpu" if host_out else dev)
+                                             for dt in layout.groups if not layout.totals[dt]}
+    with torch.no_grad(), torch.cuda.device(dev):
+        raw_stream = torch._C._cuda_getCurrentRawStream(dev.index)
+        for dt, kind, data in inputs:
+            out = outs[dt] = arena_empty(layout.totals[dt], dt, dev)
+            if kind == "flat":
+                _native.robust_nearest_reduce([data[i] for i in idx], keep, out)
+            else:
+                _native.robust_nearest_reduce_tensors_raw([p for i in idx for p in data[i]], len(idx),
+                                                          layout.split_sizes[dt], layout.byte_offsets[dt], keep,
+                                                          out.data_ptr(), _native.dtype_code(dt, single_task=True),
+                                                          raw_stream)
+    return outs
+
+
+def nearest_modules(models: List[nn.Module], keep_fn, device=None, to_host: Optional[bool] = None) -> nn.Module:
+    """The coordinate-wise mean around the median of `models` on the GPU
+    (dlsim_robust_nearest_reduce): per parameter element the n models' values
+    are sorted and the keep = keep_fn(n) of them closest to the lower median
+    are averaged in ascending order. Everything else as robust_modules: a new
+    module with copy.deepcopy(models[0]) semantics, the models only read, one
+    call per dtype group, the result where models[0] lives unless to_host says
+    otherwise; ValueError for a model whose parameter list differs from
+    models[0]'s, for more than 32 models and for a keep outside [1, n]."""
+    models[0]  # IndexError for an empty list, as FedAvg
+    n = len(models)
+    _native.check_robust_fan_in(n)
+    keep = int(keep_fn(n))
+    if not 1 <= keep <= n:
+        raise ValueError(f"mean around the median of n = {n} models: keep = {keep} must satisfy 1 <= keep <= n")
+    inputs = ModelInputs(models, _native.MAX_ROBUST_INPUTS, "median and trimmed-mean", device)
+    host_out = inputs.host_out(to_host)
+    outs = _nearest_outs(inputs, range(n), keep, host_out)
+    if not host_out and any(k is not None and len(k) for k in inputs.keep):
+        torch.cuda.current_stream(inputs.dev).synchronize()  # the staged copies' sources may go now
+    return inputs.module(outs, to_host)
+
+
+def bulyan_modules(models: List[nn.Module], f: int, to_host: Optional[bool] = None) -> nn.Module:
+    """Bulyan of `models` with Byzantine count f (gradient_aggregation/krum.py
+    has the rule): the distance matrix on the GPU (model_distances), the
+    selection of theta = n - 2f models on the host (krum.bulyan_select), then
+    the mean around the median with keep = theta - 2f over the selected models
+    in ascending index order (dlsim_robust_nearest_reduce), bit-identical to
+    nearest_modules(selected, lambda _: keep). The reduce reads the rows that
+    were resolved or staged for the distances: no model is copied twice.
+    Buffers, attributes and parameter strides are copy.deepcopy(models[0])'s,
+    also when models[0] is not selected; the result lives where models[0] lives
+    unless to_host says otherwise. One D2H copy of n*n doubles and one stream
+    synchronisation per call, as krum_modules."""
+    from dasklearn_amd.gradient_aggregation import krum as _krum
+    models[0]  # IndexError for an empty list, as FedAvg
+    n = len(models)
+    _native.check_pairdist_fan_in(n)
+    _krum.check_bulyan_params(n, f)
+    inputs = ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance")
+    chosen = _krum.bulyan_select(_distances(inputs).tolist(), f)  # waits for the stream: the staged sources may go
+    outs = _nearest_outs(inputs, chosen, len(chosen) - 2 * f, inputs.host_out(to_host))
     return inputs.module(outs, to_host)
 
 

@@ -13,7 +13,14 @@ two that keep every honest peer, GEOMETRIC_MEDIAN = 6
 `settings.aggregation_gm_nu`, default 1e-6) and CENTERED_CLIP = 7
 (`settings.aggregation_clip_tau`, default None = the lower median of the
 distances, `settings.aggregation_clip_iters`, default 3). These four defaults
-are a choice, not measured. The
+are a choice, not measured. The enum keeps the values 1 to 7; two further
+rules are variants of existing members: TRIMMED_MEAN with
+`settings.aggregation_trim_rule = "median"` (default "rank") is the mean around
+the median, MeanAroundMedian, which keeps the n - 2*`aggregation_trim` values
+closest to the median; MULTI_KRUM with `settings.aggregation_krum_rule =
+"bulyan"` (default "multi_krum") is Bulyan with Byzantine count
+`aggregation_byzantine` (`aggregation_multi_krum_m` must then be None). Any
+other string raises ValueError. The
 `dataset` argument is accepted and ignored, as the reference's aggregate task
 passes None (functions.py:99).
 """
@@ -25,8 +32,26 @@ import torch.nn as nn
 from dasklearn_amd.gradient_aggregation import GradientAggregationMethod
 from dasklearn_amd.gradient_aggregation.fedavg import FedAvg
 from dasklearn_amd.gradient_aggregation.geomed import CenteredClip, GeometricMedian
-from dasklearn_amd.gradient_aggregation.krum import Krum, MultiKrum
-from dasklearn_amd.gradient_aggregation.robust import CoordinateMedian, TrimmedMean
+from dasklearn_amd.gradient_aggregation.krum import Bulyan, Krum, MultiKrum
+from dasklearn_amd.gradient_aggregation.robust import CoordinateMedian, MeanAroundMedian, TrimmedMean
+
+
+def _rule(settings, name: str, allowed) -> str:
+    """settings.<name> (default allowed[0]); ValueError for any other value than `allowed`."""
+    rule = getattr(settings, name, allowed[0])
+    if rule not in allowed:
+        raise ValueError(f"{name} must be one of {', '.join(repr(a) for a in allowed)} (got {rule!r})")
+    return rule
+
+
+def trim_rule(settings) -> str:
+    """"rank" (TrimmedMean, the default) or "median" (MeanAroundMedian) for TRIMMED_MEAN."""
+    return _rule(settings, "aggregation_trim_rule", ("rank", "median"))
+
+
+def krum_rule_name(settings) -> str:
+    """"multi_krum" (MultiKrum, the default) or "bulyan" (Bulyan) for MULTI_KRUM."""
+    return _rule(settings, "aggregation_krum_rule", ("multi_krum", "bulyan"))
 
 
 class ModelManager:
@@ -52,12 +77,21 @@ class ModelManager:
         if method == GradientAggregationMethod.MEDIAN:
             return CoordinateMedian
         if method == GradientAggregationMethod.TRIMMED_MEAN:
-            return TrimmedMean.with_trim(getattr(self.settings, "aggregation_trim", 1))
+            trim = getattr(self.settings, "aggregation_trim", 1)
+            if trim_rule(self.settings) == "median":
+                return MeanAroundMedian.with_trim(trim)
+            return TrimmedMean.with_trim(trim)
         if method == GradientAggregationMethod.KRUM:
             return Krum.with_params(getattr(self.settings, "aggregation_byzantine", 1))
         if method == GradientAggregationMethod.MULTI_KRUM:
-            return MultiKrum.with_params(getattr(self.settings, "aggregation_byzantine", 1),
-                                         getattr(self.settings, "aggregation_multi_krum_m", None))
+            f = getattr(self.settings, "aggregation_byzantine", 1)
+            m = getattr(self.settings, "aggregation_multi_krum_m", None)
+            if krum_rule_name(self.settings) == "bulyan":
+                if m is not None:
+                    raise ValueError(f"aggregation_krum_rule = 'bulyan' selects n - 2f models itself: "
+                                     f"aggregation_multi_krum_m must be None (got {m})")
+                return Bulyan.with_params(f)
+            return MultiKrum.with_params(f, m)
         if method == GradientAggregationMethod.GEOMETRIC_MEDIAN:
             return GeometricMedian.with_params(getattr(self.settings, "aggregation_gm_iters", 3),
                                                getattr(self.settings, "aggregation_gm_nu", 1e-6))

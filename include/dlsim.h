@@ -740,6 +740,45 @@ int dlsim_robust_reduce_tensors_batched(const void* const* d_inputs, int n, int 
                                         void* stream);
 
 /*
+ * dlsim_robust_nearest_reduce: the coordinate-wise mean around the median
+ * (MeaMed / Phocas, Xie et al. 2018; the second stage of Bulyan, El Mhamdi et
+ * al. 2018) of n flat buffers. dlsim_robust_reduce with a window chosen per
+ * element: the `keep` sorted values closest to the lower median. (New: it
+ * replaces no reference code.) Per element j, over the n values
+ * d_inputs[i][j]:
+ *   s    = the values sorted ascending in dlsim_robust_reduce's total order
+ *   m    = (n-1)/2, p = s[m]
+ *   d[k] = +0.0 where s[k] has the same sort key as p (the same value class
+ *          and bits; any two NaNs), else fl(|s[k] - p|): one subtraction in
+ *          the accumulator type (fp32 for fp32, bf16 and fp16, whose widening
+ *          is exact; fp64 for fp64). Ranked 0 <= ... <= +Inf < NaN.
+ *   the window [lo, lo+keep) starts as [m, m+1) and grows keep - 1 times: by
+ *   the right neighbour iff it exists and the left neighbour does not exist or
+ *   is strictly farther; ties go left
+ *   acc = s[lo];  for k = lo+1 .. lo+keep-1: acc = acc + s[k]
+ *   d_out[j] = acc / keep      (rounding and NaN canonicalisation as
+ *                               dlsim_robust_reduce)
+ * keep = 1 is the lower median and keep = n the window [0, n): both equal
+ * dlsim_robust_reduce bit for bit.
+ *   n      1 <= n <= DLSIM_MAX_ROBUST_INPUTS
+ *   keep   1 <= keep <= n (DLSIM_E_ARG otherwise)
+ * Buffers, dtypes, alignment, n_elems == 0, the overlap rule and the order of
+ * the checks (all before any HIP call) are dlsim_robust_reduce's.
+ * Stream-ordered.
+ */
+int dlsim_robust_nearest_reduce(const void* const* d_inputs, int n, int keep, void* d_out, size_t n_elems, int dtype,
+                                void* stream);
+
+/*
+ * dlsim_robust_nearest_reduce_tensors: dlsim_robust_nearest_reduce over t
+ * separate tensors per model, with dlsim_robust_reduce_tensors's arguments and
+ * checks: one launch per non-empty tensor, in order, bit-identical to t
+ * dlsim_robust_nearest_reduce calls.
+ */
+int dlsim_robust_nearest_reduce_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                        const size_t* out_off_bytes, int keep, void* d_out, int dtype, void* stream);
+
+/*
  * dlsim_pairwise_sqdist: the matrix of squared L2 distances between n flat
  * buffers, the primitive under Krum and Multi-Krum and the consensus distance
  * of decentralized-learning papers.

@@ -28,8 +28,16 @@ same bytes (for DESIGN.md §8j).
            synchronised); (d) one fp32 task of 11,181,642 elements, n = 8,
            through the batched entry against the flat entry.
 
+  nearest  (--nearest, instead of the above) the mean around the
+           median, dlsim_robust_nearest_reduce with keep = n - 2, against
+           dlsim_robust_reduce with the rank window [1, n-1) of the same kept
+           count: the same buffers, rotation and decoy rule in this one
+           process, the yardstick before and after; fp32 at 11,181,642
+           elements with n = 4, 8, 16, 32 and bf16 at 125,000,000 with n = 8.
+
     python scripts/bench_robust.py [--windows 5] [--launches 200] [--skip-bf16]
     python scripts/bench_robust.py --batch [--windows 5] [--legs abcd]
+    python scripts/bench_robust.py --nearest [--windows 5] [--launches 200] [--skip-bf16]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -135,6 +143,55 @@ def kernel_lines(P, tdt, n, launches, nwin):
     if "trim_1" in res:
         ratio["trim_1_over_yard"] = round(res["trim_1"] / yard_us, 4)
     print(json.dumps(ratio), flush=True)
+
+
+# ---- the mean around the median (--nearest) ------------------------------------------------
+def nearest_plan(inputs, keep, out):
+    n = len(inputs)
+    args = ((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, keep, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            _native.dtype_code(out.dtype, single_task=True))
+    return Call("dlsim_robust_nearest_reduce", args, out.device, (list(inputs), out))
+
+
+def nearest_lines(P, tdt, n, launches, nwin):
+    """dlsim_robust_nearest_reduce with keep = n - 2 against its yardstick, dlsim_robust_reduce with the rank window
+    of the same kept count ([1, n-1)): the same loads, sort, adds and stores, so the ratio is the price of the
+    distances, the window choice and the predicated sum. kernel_lines' buffers, rotation and decoy rule."""
+    dev = torch.device("cuda", 0)
+    esz = torch.empty((), dtype=tdt).element_size()
+    byts = (n + 1) * P * esz
+    sets = max(3, -(-(1 << 30) // (n * P * esz)))
+    out_sets = -(-max(sets, -(-(1 << 30) // (P * esz))) // sets) * sets
+    stride = row_stride(P, esz)
+    rows = aligned_empty((sets + 1) * n * stride, tdt, dev, base_align(P * esz, esz)).view(sets + 1, n, stride)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for s in range(sets + 1):
+        for i in range(n):
+            rows[s, i, :P].copy_((torch.randn(P, generator=g, device=dev) * 0.05).to(tdt))
+    outs = [arena_empty(P, tdt, dev) for _ in range(out_sets + 1)]
+    ins = [[rows[s, i, :P] for i in range(n)] for s in range(sets + 1)]
+    keep, win = n - 2, (1, n - 1)
+    decoy = nearest_plan(ins[sets], keep, outs[out_sets])
+    for _ in range(8):
+        decoy.launch()
+    torch.cuda.synchronize()
+    base = {"bench": "robust_nearest", "params": P, "dtype": str(tdt).replace("torch.", ""), "n": n, "keep": keep,
+            "bytes": byts, "rotating_sets": sets, "rotating_outputs": out_sets, "launches_per_window": launches,
+            "windows": nwin}
+    shape = "halves" if n > 16 else "tiles"
+    res, yards = {}, []
+    for leg in ("rank_1", "nearest", "rank_2"):
+        if leg == "nearest":
+            plans = [nearest_plan(ins[j % sets], keep, outs[j]) for j in range(out_sets)]
+        else:
+            plans = [RobustPlan(ins[j % sets], *win, outs[j]) for j in range(out_sets)]
+        ws = windows(plans, launches, nwin)
+        res[leg] = report(base, leg, ws, GBps=round(byts / ws[len(ws) // 2] / 1e3, 1),
+                          kernel=f"dlsim::k_nearest_{shape}" if leg == "nearest" else f"dlsim::k_robust_{shape}")
+        if leg != "nearest":
+            yards.append(res[leg])
+    res["rank"] = sum(yards) / 2
+    ratio_line(base, "ratio", res, "nearest", "rank", yards)
 
 
 # ---- the batched entries (--batch) ---------------------------------------------------------
@@ -392,9 +449,18 @@ def main():
     ap.add_argument("--skip-bf16", action="store_true")
     ap.add_argument("--batch", action="store_true", help="the batched entries' legs (a)-(d) instead of the flat kernel's")
     ap.add_argument("--legs", default="abcd", help="with --batch: which of the legs a, b, c, d")
+    ap.add_argument("--nearest", action="store_true",
+                    help="dlsim_robust_nearest_reduce against dlsim_robust_reduce instead of the flat kernel's legs")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_robust.py measures on a GPU; none is visible")
+    if a.nearest:
+        for n in (4, 8, 16, 32):
+            nearest_lines(RESNET18_P, torch.float32, n, a.launches, a.windows)
+            torch.cuda.empty_cache()
+        if not a.skip_bf16:
+            nearest_lines(125_000_000, torch.bfloat16, 8, a.launches, a.windows)
+        return
     if a.batch:
         for leg in a.legs:
             {"a": lambda: leg_a(a.windows, 20), "b": lambda: leg_b(a.windows, 40), "c": lambda: leg_c(a.windows),

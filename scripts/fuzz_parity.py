@@ -41,7 +41,9 @@ shapes, dtypes, alignments, weights and special values, for a time budget.
               coordinate median and trimmed mean): random fan-in 1..32, window,
               dtype (all four), size, alignment of every input and of the
               output, special values, vs tests/_robust_util.py's restatement of
-              the contract
+              the contract; then dlsim_robust_nearest_reduce
+              and its tensors entry (the mean around the median, §8q) on the
+              same inputs with a random kept count, vs tests/_nearest_util.py
   robust_batch  dlsim_robust_reduce_batched and dlsim_robust_reduce_tensors_batched
               (DESIGN.md §8m): 1..40 tasks of random fan-in 1..32 (all
               capacity classes in one call), window, size (empty ones too) and
@@ -525,7 +527,20 @@ def robust_case(rng, dtype):
                                       lo, hi, out2.data_ptr(), _native.dtype_code(dt, single_task=True),
                                       torch.cuda.current_stream().cuda_stream)
     ok = ok and ru.same_bits(out2.cpu(), exp)
-    return ok, dict(kind="robust", dtype=dtype, n=n, lo=lo, hi=hi, sizes=sizes)
+    # the mean around the median (dlsim_robust_nearest_reduce) on the same inputs, both entries
+    import _nearest_util as nu
+    keep = int(rng.choice([1, n, (n + 1) // 2, int(rng.integers(1, n + 1))]))
+    exp = nu.nearest_mean(xs, keep)
+    out3 = dev(torch.zeros(total, dtype=dt))
+    _native.robust_nearest_reduce(flat, keep, out3)
+    ok = ok and ru.same_bits(out3.cpu(), exp)
+    out4 = dev(torch.zeros(total, dtype=dt))
+    _native.robust_nearest_reduce_tensors_raw([t.data_ptr() for row in parts for t in row], n, sizes,
+                                              [o * esz for o in offs], keep, out4.data_ptr(),
+                                              _native.dtype_code(dt, single_task=True),
+                                              torch.cuda.current_stream().cuda_stream)
+    ok = ok and ru.same_bits(out4.cpu(), exp)
+    return ok, dict(kind="robust", dtype=dtype, n=n, lo=lo, hi=hi, keep=keep, sizes=sizes)
 
 
 def robust_batch_case(rng, dtype):
