@@ -19,6 +19,7 @@
 #include "abi_common.hpp"
 #include "dispatch.hpp"
 #include "fanin_checks.hpp"
+#include "partials.hpp"
 
 // Every DLSIM_* switch named below is an A/B switch, read through
 // dlsim::ab_getenv: only when DLSIM_AB=1 is set as well (ab_env.hpp).
@@ -328,11 +329,28 @@ hipError_t reducedist_batched(int b, const int* fan_in, const int* n_tensors, co
                               const size_t* nelem, const size_t* out_off, const double* w, void* const* outs,
                               int dtype, double* const* d2s, int accumulate, hipStream_t st);
 void reducedist_batch_geometry(int dtype, int* max_segments, int* max_ptrs);
+// top-k sharing (inst_topk.hip, inst_sparse_reduce.hip; the geometries are partials.hpp's)
+hipError_t topk_select(const void* x, void* ref, size_t nelem, uint32_t k, int dtype, int32_t* idx, void* val,
+                       uint32_t* threshold, hipStream_t st);
+const char* topk_kernel_name(bool vec);
+hipError_t sparse_run(int b, const void* const* self, const int* m, const int32_t* const* idx, const void* const* val,
+                      const long long* k, const float* w, void* const* out, const size_t* nelem, int dtype,
+                      hipStream_t st);
+const char* sparse_kernel_name(bool vec);
+void sparse_batch_limits(int* max_tasks, int* max_slots);
 
 // why each family stops at its DLSIM_MAX_*_INPUTS (check_fan_in, fanin_checks.hpp)
 constexpr const char* kRobustLimit = "the sorting network is held in registers";
 constexpr const char* kPairdistLimit = "the pairs' accumulators are held in registers";
 constexpr const char* kReducedistLimit = "the inputs' rows and accumulators are held in registers";
+constexpr const char* kSparseLimit = "the 32-row bound of the robust, distance and reduce-and-measure entries";
+
+// the dtypes of the top-k sharing entries
+int check_sharing_dtype(int dtype, const char* entry) {
+  if (dtype == DLSIM_F32 || dtype == DLSIM_BF16) return DLSIM_OK;
+  return fail(DLSIM_E_DTYPE, "%s takes DLSIM_F32 and DLSIM_BF16 (got dtype %d): the dtypes of the shipped configurations",
+              entry, dtype);
+}
 
 // the order-statistic window of dlsim_robust_reduce / _tensors
 int check_robust_window(int n, int lo, int hi) {
@@ -1521,6 +1539,158 @@ int dlsim_reducedist_batch_geometry(int n, int dtype, int* max_segments, int* ma
   if (!max_segments || !max_ptrs) return fail(DLSIM_E_ARG, "null result pointer");
   reducedist_batch_geometry(dtype, max_segments, max_ptrs);
   return DLSIM_OK;
+}
+
+// ---- top-k sparsified sharing ----------------------------------------------------
+namespace {
+
+constexpr size_t kSharingMaxElems = size_t{1} << 31;  // indices are int32
+
+bool ranges_meet(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  return a_bytes && b_bytes && addr(a) < addr(b) + b_bytes && addr(b) < addr(a) + a_bytes;
+}
+
+}  // namespace
+
+int dlsim_topk_select(const void* d_x, void* d_ref, size_t n_elems, long long k, int dtype, int32_t* d_idx, void* d_val,
+                      uint32_t* d_threshold, void* stream) {
+  g_err.clear();
+  int rc = check_sharing_dtype(dtype, "dlsim_topk_select");
+  if (rc != DLSIM_OK) return rc;
+  if (n_elems >= kSharingMaxElems) return fail(DLSIM_E_ARG, "n_elems must be < 2^31 (got %zu): indices are int32", n_elems);
+  if (k < 0 || static_cast<unsigned long long>(k) > n_elems)
+    return fail(DLSIM_E_ARG, "k must satisfy 0 <= k <= n_elems (got k %lld, n_elems %zu)", k, n_elems);
+  if (k == 0) return DLSIM_OK;  // nothing selected, nothing launched (n_elems == 0 ends here too)
+  if (!d_x || !d_ref) return fail(DLSIM_E_ARG, "null model or last-shared pointer");
+  if (!d_idx || !d_val) return fail(DLSIM_E_ARG, "null index or value output pointer");
+  const size_t esz = elem_bytes(dtype), bytes = n_elems * esz;
+  const size_t ib = static_cast<size_t>(k) * sizeof(int32_t), vb = static_cast<size_t>(k) * esz;
+  if (ranges_meet(d_x, bytes, d_ref, bytes)) return fail(DLSIM_E_ARG, "the model overlaps the last-shared copy");
+  if (ranges_meet(d_ref, bytes, d_idx, ib)) return fail(DLSIM_E_ARG, "the last-shared copy overlaps the index output");
+  if (ranges_meet(d_ref, bytes, d_val, vb)) return fail(DLSIM_E_ARG, "the last-shared copy overlaps the value output");
+  if (ranges_meet(d_x, bytes, d_idx, ib)) return fail(DLSIM_E_ARG, "the model overlaps the index output");
+  if (ranges_meet(d_x, bytes, d_val, vb)) return fail(DLSIM_E_ARG, "the model overlaps the value output");
+  if (ranges_meet(d_idx, ib, d_val, vb)) return fail(DLSIM_E_ARG, "the index output overlaps the value output");
+  if (d_threshold && (ranges_meet(d_threshold, 4, d_ref, bytes) || ranges_meet(d_threshold, 4, d_x, bytes) ||
+                      ranges_meet(d_threshold, 4, d_idx, ib) || ranges_meet(d_threshold, 4, d_val, vb)))
+    return fail(DLSIM_E_ARG, "the threshold output overlaps another buffer");
+  const hipError_t e = topk_select(d_x, d_ref, n_elems, static_cast<uint32_t>(k), dtype, d_idx, d_val, d_threshold,
+                                   static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "top-k selection launch");
+}
+
+int dlsim_topk_geometry(size_t n_elems, int dtype, size_t* vec_tile_elems, size_t* block_tile_elems,
+                        unsigned* max_blocks, unsigned* blocks, size_t* workspace_bytes) {
+  g_err.clear();
+  const int rc = check_sharing_dtype(dtype, "dlsim_topk_geometry");
+  if (rc != DLSIM_OK) return rc;
+  if (n_elems >= kSharingMaxElems) return fail(DLSIM_E_ARG, "n_elems must be < 2^31 (got %zu): indices are int32", n_elems);
+  if (!vec_tile_elems || !block_tile_elems || !max_blocks || !blocks || !workspace_bytes)
+    return fail(DLSIM_E_ARG, "null result pointer");
+  const TopkGeom g = topk_geometry(n_elems, dtype);
+  *vec_tile_elems = g.vec_tile;
+  *block_tile_elems = g.block_tile;
+  *max_blocks = g.max_blocks;
+  *blocks = g.blocks;
+  *workspace_bytes = g.ws_bytes;
+  return DLSIM_OK;
+}
+
+const char* dlsim_topk_kernel_name(const void* d_x, const void* d_ref, size_t n_elems, long long k, int dtype) {
+  if ((dtype != DLSIM_F32 && dtype != DLSIM_BF16) || k < 1 || static_cast<unsigned long long>(k) > n_elems) return "";
+  return topk_kernel_name(aligned16(d_x) && aligned16(d_ref));
+}
+
+int dlsim_sparse_wreduce_batched(int b, const void* const* d_self, const int* m, const int32_t* const* d_idx,
+                                 const void* const* d_val, const long long* k, const float* h_weights,
+                                 void* const* d_out, const size_t* n_elems, int dtype, void* stream) {
+  g_err.clear();
+  int rc = check_sharing_dtype(dtype, "dlsim_sparse_wreduce");
+  if (rc != DLSIM_OK) return rc;
+  if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
+  if (b == 0) return DLSIM_OK;
+  if (!d_self || !m || !h_weights || !d_out || !n_elems) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  struct Rd {  // a range some task reads: its dense row or one of its lists
+    uintptr_t a, b;
+    int task;
+  };
+  std::vector<Rd> reads;
+  std::vector<Span> writes;
+  size_t slot = 0;
+  for (int t = 0; t < b; ++t) {
+    if (m[t] < 0) return fail(DLSIM_E_ARG, "task %d: m must be >= 0 (got %d)", t, m[t]);
+    rc = check_fan_in(m[t] + 1, DLSIM_MAX_SPARSE_NEIGHBOURS + 1, dtype, kSparseLimit);
+    if (rc != DLSIM_OK) return fail(rc, "task %d: %s", t, std::string(g_err).c_str());
+    if (m[t] > 0 && (!d_idx || !d_val || !k)) return fail(DLSIM_E_ARG, "null array argument");
+    const size_t P = n_elems[t];
+    if (P >= kSharingMaxElems)
+      return fail(DLSIM_E_ARG, "task %d: n_elems must be < 2^31 (got %zu): indices are int32", t, P);
+    if (P && (!d_self[t] || !d_out[t])) return fail(DLSIM_E_ARG, "task %d: null dense row or output pointer", t);
+    if (P) {
+      const uintptr_t s0 = addr(d_self[t]), o0 = addr(d_out[t]);
+      if (s0 != o0 && s0 < o0 + P * esz && o0 < s0 + P * esz)
+        return fail(DLSIM_E_ARG, "task %d: output partially overlaps the dense row", t);
+      reads.push_back({s0, s0 + P * esz, t});
+      writes.push_back({o0, o0 + P * esz, t});
+    }
+    for (int j = 0; j < m[t]; ++j, ++slot) {
+      const long long kj = k[slot];
+      if (kj < 0 || static_cast<unsigned long long>(kj) > P)
+        return fail(DLSIM_E_ARG, "task %d, neighbour %d: k must satisfy 0 <= k <= n_elems (got k %lld, n_elems %zu)", t,
+                    j, kj, P);
+      if (kj == 0) continue;  // never read: any pointer will do
+      if (!d_idx[slot] || !d_val[slot])
+        return fail(DLSIM_E_ARG, "task %d, neighbour %d: null index or value pointer", t, j);
+      reads.push_back({addr(d_idx[slot]), addr(d_idx[slot]) + static_cast<size_t>(kj) * sizeof(int32_t), -1 - t});
+      reads.push_back({addr(d_val[slot]), addr(d_val[slot]) + static_cast<size_t>(kj) * esz, -1 - t});
+    }
+  }
+  // one launch runs its tasks concurrently: an output shares bytes with nothing but its own dense row
+  std::sort(writes.begin(), writes.end(), [](const Span& x, const Span& y) { return x.a < y.a; });
+  for (size_t i = 1; i < writes.size(); ++i)
+    if (writes[i].a < writes[i - 1].b)
+      return fail(DLSIM_E_ARG, "the outputs of tasks %d and %d overlap", writes[i - 1].task, writes[i].task);
+  for (const Rd& r : reads) {
+    auto it = std::upper_bound(writes.begin(), writes.end(), r.a, [](uintptr_t v, const Span& x) { return v < x.b; });
+    for (; it != writes.end() && it->a < r.b; ++it) {
+      if (r.task == it->task) continue;  // a task's own dense row (exact or no overlap: checked above)
+      if (r.task < 0)
+        return fail(DLSIM_E_ARG, "the output of task %d overlaps an index or value list of task %d", it->task,
+                    -1 - r.task);
+      return fail(DLSIM_E_ARG, "the output of task %d overlaps the dense row of task %d", it->task, r.task);
+    }
+  }
+  const hipError_t e = sparse_run(b, d_self, m, d_idx, d_val, k, h_weights, d_out, n_elems, dtype,
+                                  static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "sparse reduce launch");
+}
+
+int dlsim_sparse_wreduce(const void* d_self, int m, const int32_t* const* d_idx, const void* const* d_val,
+                         const long long* k, const float* h_weights, void* d_out, size_t n_elems, int dtype,
+                         void* stream) {
+  return dlsim_sparse_wreduce_batched(1, &d_self, &m, d_idx, d_val, k, h_weights, &d_out, &n_elems, dtype, stream);
+}
+
+int dlsim_sparse_geometry(size_t n_elems, int dtype, size_t* tile_elems, unsigned* max_blocks, unsigned* blocks,
+                          int* max_tasks, int* max_neighbours) {
+  g_err.clear();
+  const int rc = check_sharing_dtype(dtype, "dlsim_sparse_geometry");
+  if (rc != DLSIM_OK) return rc;
+  if (n_elems >= kSharingMaxElems) return fail(DLSIM_E_ARG, "n_elems must be < 2^31 (got %zu): indices are int32", n_elems);
+  if (!tile_elems || !max_blocks || !blocks || !max_tasks || !max_neighbours)
+    return fail(DLSIM_E_ARG, "null result pointer");
+  const SparseGeom g = sparse_geometry(n_elems, dtype);
+  *tile_elems = g.tile;
+  *max_blocks = g.max_blocks;
+  *blocks = g.blocks;
+  sparse_batch_limits(max_tasks, max_neighbours);
+  return DLSIM_OK;
+}
+
+const char* dlsim_sparse_kernel_name(const void* d_self, const void* d_out, size_t n_elems, int dtype) {
+  if ((dtype != DLSIM_F32 && dtype != DLSIM_BF16) || n_elems == 0) return "";
+  return sparse_kernel_name(aligned16(d_self) && aligned16(d_out));
 }
 
 int dlsim_device_alloc(size_t nbytes, int flags, void** d_out, int* contiguous) {

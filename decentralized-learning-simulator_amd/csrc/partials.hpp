@@ -62,6 +62,28 @@ struct RdGeom {
 // vec: every base is 16-byte aligned
 RdGeom rd_geometry(int n, int elem_bytes, size_t nelem, bool vec);
 
+// The grid and workspace of one top-k selection (inst_topk.hip defines topk_geometry): a block owns
+// tpb consecutive tiles of block_tile elements, the same ones in every pass.
+struct TopkGeom {
+  size_t vec_tile;      // elements of one row of a tile: a 16-byte vector per lane
+  size_t block_tile;    // elements of a tile
+  unsigned max_blocks;  // the grid's cap: past max_blocks * block_tile elements a block takes several tiles
+  unsigned tpb;         // tiles per block
+  unsigned blocks;      // grid of every pass (0 for no element)
+  size_t ws_bytes;      // the call's workspace: three histograms, state words, two counts per block
+};
+TopkGeom topk_geometry(size_t nelem, int dtype);
+
+// The virtual grid of one sparse mixing task (inst_sparse_reduce.hip defines sparse_geometry), which a
+// batched launch gives every task unchanged.
+struct SparseGeom {
+  size_t tile;          // coordinates of a tile
+  unsigned max_blocks;  // the grid's cap
+  unsigned tpb;         // consecutive tiles per block
+  unsigned blocks;      // grid (0 for no element)
+};
+SparseGeom sparse_geometry(size_t nelem, int dtype);
+
 inline unsigned finish_blocks(int items) {  // grid of a finish kernel: one wave per item (a pair, an input)
   return static_cast<unsigned>((items + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
 }

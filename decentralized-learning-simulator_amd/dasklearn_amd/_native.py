@@ -79,6 +79,13 @@ EXPORTS = (
     "dlsim_wreduce_dist",
     "dlsim_wreduce_dist_tensors",
     "dlsim_reducedist_geometry",
+    "dlsim_topk_select",
+    "dlsim_topk_geometry",
+    "dlsim_topk_kernel_name",
+    "dlsim_sparse_wreduce",
+    "dlsim_sparse_wreduce_batched",
+    "dlsim_sparse_geometry",
+    "dlsim_sparse_kernel_name",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -264,6 +271,25 @@ def load() -> ctypes.CDLL:
         lib.dlsim_wreduce_dist_batched.restype = i
         lib.dlsim_reducedist_batch_geometry.argtypes = [i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
         lib.dlsim_reducedist_batch_geometry.restype = i
+        ll, uip = ctypes.c_longlong, ctypes.POINTER(ctypes.c_uint)
+        lib.dlsim_topk_select.argtypes = [vp, vp, sz, ll, i, vp, vp, vp, vp]
+        lib.dlsim_topk_select.restype = i
+        lib.dlsim_topk_geometry.argtypes = [sz, i, ctypes.POINTER(sz), ctypes.POINTER(sz), uip, uip, ctypes.POINTER(sz)]
+        lib.dlsim_topk_geometry.restype = i
+        lib.dlsim_topk_kernel_name.argtypes = [vp, vp, sz, ll, i]
+        lib.dlsim_topk_kernel_name.restype = ctypes.c_char_p
+        lib.dlsim_sparse_wreduce.argtypes = [vp, i, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ll),
+                                             ctypes.POINTER(ctypes.c_float), vp, sz, i, vp]
+        lib.dlsim_sparse_wreduce.restype = i
+        lib.dlsim_sparse_wreduce_batched.argtypes = [i, ctypes.POINTER(vp), ctypes.POINTER(i), ctypes.POINTER(vp),
+                                                     ctypes.POINTER(vp), ctypes.POINTER(ll),
+                                                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(vp),
+                                                     ctypes.POINTER(sz), i, vp]
+        lib.dlsim_sparse_wreduce_batched.restype = i
+        lib.dlsim_sparse_geometry.argtypes = [sz, i, ctypes.POINTER(sz), uip, uip, ctypes.POINTER(i), ctypes.POINTER(i)]
+        lib.dlsim_sparse_geometry.restype = i
+        lib.dlsim_sparse_kernel_name.argtypes = [vp, vp, sz, i]
+        lib.dlsim_sparse_kernel_name.restype = ctypes.c_char_p
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -645,6 +671,145 @@ def robust_nearest_reduce(inputs, keep: int, out, stream=None):
            load().dlsim_robust_nearest_reduce(_ptr_array([t.data_ptr() for t in inputs]), n, int(keep),
                                               out.data_ptr(), numel, dtype_code(dt, single_task=True),
                                               _stream_handle(out.device, stream)))
+    return out
+
+
+# ---- top-k sparsified sharing: selection and the sparse neighbour reduce ----
+MAX_SPARSE_NEIGHBOURS = 31  # include/dlsim.h DLSIM_MAX_SPARSE_NEIGHBOURS
+
+
+def sharing_dtype_code(torch_dtype) -> int:
+    """ABI dtype of the top-k sharing entries: fp32 and bf16 only."""
+    import torch
+    if torch_dtype == torch.float32:
+        return DLSIM_F32
+    if torch_dtype == torch.bfloat16:
+        return DLSIM_BF16
+    raise TypeError(f"top-k sharing supports float32 and bfloat16 parameters, got {torch_dtype}")
+
+
+def topk_geometry(numel: int, torch_dtype) -> dict:
+    """dlsim_topk_geometry: vec_tile, block_tile, max_blocks, blocks and workspace_bytes of a selection."""
+    vt, bt, ws = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    mb, nb = ctypes.c_uint(0), ctypes.c_uint(0)
+    _check("dlsim_topk_geometry",
+           load().dlsim_topk_geometry(numel, sharing_dtype_code(torch_dtype), ctypes.byref(vt), ctypes.byref(bt),
+                                      ctypes.byref(mb), ctypes.byref(nb), ctypes.byref(ws)))
+    return {"vec_tile": vt.value, "block_tile": bt.value, "max_blocks": mb.value, "blocks": nb.value,
+            "workspace_bytes": ws.value}
+
+
+def topk_kernel_name(x, ref, k: int) -> str:
+    return load().dlsim_topk_kernel_name(x.data_ptr(), ref.data_ptr(), x.numel(), int(k),
+                                         sharing_dtype_code(x.dtype)).decode()
+
+
+def topk_select(x, ref, k: int, idx, val, threshold=None, stream=None):
+    """dlsim_topk_select: the k coordinates of the flat device tensor `x` that
+    moved most since `ref` (same dtype and size; updated in place at the
+    selected coordinates), lowest index first among ties: `idx` (int32, k,
+    ascending) and `val` (x's dtype, k). `threshold`: an optional one-element
+    int32 device tensor for the threshold key. Stream-ordered."""
+    import torch
+    dt = sharing_dtype_code(x.dtype)
+    for t in (x, ref, idx, val) + (() if threshold is None else (threshold,)):
+        if not t.is_cuda or t.device != x.device or not t.is_contiguous():
+            raise ValueError("top-k selection needs contiguous device tensors on one device (no CPU path)")
+    if ref.dtype != x.dtype or ref.numel() != x.numel() or val.dtype != x.dtype:
+        raise ValueError("model, last-shared copy and values must have one dtype; model and copy one size")
+    if idx.dtype != torch.int32 or idx.numel() != k or val.numel() != k:
+        raise ValueError(f"indices must be int32 and hold k = {k} elements, like the values")
+    if threshold is not None and (threshold.dtype != torch.int32 or threshold.numel() != 1):
+        raise ValueError("the threshold must be a one-element int32 tensor")
+    _check("dlsim_topk_select",
+           load().dlsim_topk_select(x.data_ptr(), ref.data_ptr(), x.numel(), int(k), dt, idx.data_ptr(), val.data_ptr(),
+                                    None if threshold is None else threshold.data_ptr(),
+                                    _stream_handle(x.device, stream)))
+    return idx, val
+
+
+def sparse_geometry(numel: int, torch_dtype) -> dict:
+    """dlsim_sparse_geometry: tile, max_blocks and blocks of a task, max_tasks and max_neighbours of a launch."""
+    tile, mb, nb = ctypes.c_size_t(0), ctypes.c_uint(0), ctypes.c_uint(0)
+    mt, mn = ctypes.c_int(0), ctypes.c_int(0)
+    _check("dlsim_sparse_geometry",
+           load().dlsim_sparse_geometry(numel, sharing_dtype_code(torch_dtype), ctypes.byref(tile), ctypes.byref(mb),
+                                        ctypes.byref(nb), ctypes.byref(mt), ctypes.byref(mn)))
+    return {"tile": tile.value, "max_blocks": mb.value, "blocks": nb.value, "max_tasks": mt.value,
+            "max_neighbours": mn.value}
+
+
+def sparse_kernel_name(own, out) -> str:
+    return load().dlsim_sparse_kernel_name(own.data_ptr(), out.data_ptr(), own.numel(),
+                                           sharing_dtype_code(own.dtype)).decode()
+
+
+def check_sparse_fan_in(m: int) -> None:
+    _check_fan_in(m + 1, MAX_SPARSE_NEIGHBOURS + 1, "the sparse mixing kernel takes at most {limit} models, the "
+                                                    "receiver's own included (got {n})")
+
+
+def sparse_wreduce_batched(tasks, stream=None):
+    """dlsim_sparse_wreduce_batched over tasks (own, [(idx, val), ...],
+    weights_f32, out): flat device tensors of one dtype on one device; idx
+    int32 ascending, val of own's dtype; weights own's first. out may be own.
+    Stream-ordered; the tensors must outlive the launches."""
+    import torch
+    if not tasks:
+        return
+    dev, tdt = tasks[0][3].device, tasks[0][0].dtype
+    dt = sharing_dtype_code(tdt)
+    selfs, ms, idxs, vals, ks, ws, outs, ns = [], [], [], [], [], [], [], []
+    for own, lists, w, out in tasks:
+        check_sparse_fan_in(len(lists))
+        if len(w) != len(lists) + 1:
+            raise AssertionError("weights/models length mismatch")
+        for t in (own, out):
+            if not t.is_cuda or t.device != dev or t.dtype != tdt or not t.is_contiguous() or t.numel() != own.numel():
+                raise ValueError("the sparse reduce needs contiguous device tensors of one dtype, size and device")
+        for ix, vl in lists:
+            if (not ix.is_cuda or not vl.is_cuda or ix.device != dev or vl.device != dev or ix.dtype != torch.int32
+                    or vl.dtype != tdt or ix.numel() != vl.numel() or not ix.is_contiguous() or not vl.is_contiguous()):
+                raise ValueError("a sparse neighbour is int32 indices and as many values of the model's dtype, on its device")
+            idxs.append(ix.data_ptr())
+            vals.append(vl.data_ptr())
+            ks.append(ix.numel())
+        selfs.append(own.data_ptr())
+        outs.append(out.data_ptr())
+        ms.append(len(lists))
+        ns.append(own.numel())
+        ws += [float(v) for v in w]
+    b = len(tasks)
+    _check("dlsim_sparse_wreduce_batched",
+           load().dlsim_sparse_wreduce_batched(b, _ptr_array(selfs), (ctypes.c_int * b)(*ms), _ptr_array(idxs),
+                                               _ptr_array(vals), (ctypes.c_longlong * max(len(ks), 1))(*ks),
+                                               (ctypes.c_float * len(ws))(*ws), _ptr_array(outs), _size_array(ns), dt,
+                                               _stream_handle(dev, stream)))
+
+
+def sparse_wreduce(own, lists, weights_f32, out, stream=None):
+    """dlsim_sparse_wreduce: out = the exact weighted reduce of `own` and the
+    sparse neighbours `lists` ([(idx, val), ...]), each densified over own."""
+    import torch
+    check_sparse_fan_in(len(lists))
+    if len(weights_f32) != len(lists) + 1:
+        raise AssertionError("weights/models length mismatch")
+    dt = sharing_dtype_code(own.dtype)
+    for t in [own, out] + [t for pair in lists for t in pair]:
+        if not t.is_cuda or t.device != out.device or not t.is_contiguous():
+            raise ValueError("the sparse reduce needs contiguous device tensors on one device (no CPU path)")
+    if out.dtype != own.dtype or out.numel() != own.numel():
+        raise ValueError("the dense row and the output must have one dtype and size")
+    for ix, vl in lists:
+        if ix.dtype != torch.int32 or vl.dtype != own.dtype or ix.numel() != vl.numel():
+            raise ValueError("a sparse neighbour is int32 indices and as many values of the model's dtype")
+    m = len(lists)
+    _check("dlsim_sparse_wreduce",
+           load().dlsim_sparse_wreduce(own.data_ptr(), m, _ptr_array([ix.data_ptr() for ix, _ in lists]),
+                                       _ptr_array([vl.data_ptr() for _, vl in lists]),
+                                       (ctypes.c_longlong * max(m, 1))(*[ix.numel() for ix, _ in lists]),
+                                       (ctypes.c_float * (m + 1))(*[float(v) for v in weights_f32]), out.data_ptr(),
+                                       own.numel(), dt, _stream_handle(out.device, stream)))
     return out
 
 

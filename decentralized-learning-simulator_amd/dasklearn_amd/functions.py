@@ -12,6 +12,7 @@ params: {"models": [nn.Module], "round": int, "peer": int | None,
 broker requires list/tuple results, broker.py:282-283).
 """
 import logging
+import threading
 import time
 from typing import Dict, List
 
@@ -21,7 +22,24 @@ from dasklearn_amd.model_manager import ModelManager
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["aggregate", "gradient_update", "chunk", "reconstruct_from_chunks"]
+__all__ = ["aggregate", "gradient_update", "chunk", "reconstruct_from_chunks", "sparsify", "aggregate_sparse",
+           "reset_sharers"]
+
+# One TopKSharer per (session, peer), kept in the worker between tasks: the
+# last-shared copy is the state of top-k sharing (sparsify below). Guarded by
+# a lock (a worker may run tasks on several threads); reset_sharers() drops it.
+_sharers: Dict = {}
+_sharers_lock = threading.Lock()
+
+
+def reset_sharers(session=None) -> None:
+    """Forget the last-shared copies of `session` (params["session"] of the
+    sparsify tasks; None: of every session). A process that runs one
+    simulation after another under the same session key calls this between
+    them, or the next run would start from the previous run's copies."""
+    with _sharers_lock:
+        for key in [k for k in _sharers if session is None or k[0] == session]:
+            del _sharers[key]
 
 # The reference builds the model to reconstruct into from its model zoo
 # (functions.py:144, dasklearn.models.create_model). Out of scope here, so it
@@ -75,6 +93,45 @@ def gradient_update(settings, params: Dict) -> List[nn.Module]:
     learning = settings.learning
     return [sgd_step_module(model, params["gradient_model"].gradient, learning.learning_rate, learning.momentum,
                             learning.weight_decay)]
+
+
+def sparsify(settings, params: Dict) -> List:
+    """New (the reference shares dense models only): params {"model", "peer",
+    "k" | "ratio", optional "session"} -> [SparseModel], the k coordinates of
+    the peer's model that moved most since it last shared them
+    (dasklearn_amd/sparse.py). The worker keeps one TopKSharer per (session,
+    peer): "session" (default: settings.session_id if it has one, else None)
+    keeps simulations that share a worker process apart, and reset_sharers()
+    drops the copies between runs. A peer whose k, ratio or parameter list
+    changes starts over from a zero last-shared copy. A peer's sharer is
+    locked while it shares, so tasks of one peer on several threads run one
+    after the other."""
+    from dasklearn_amd.arena import layout_of
+    from dasklearn_amd.sparse import TopKSharer
+    model = params["model"]
+    if isinstance(model, tuple):  # the first round's (model, 0), functions.py:31-32
+        model = model[0]
+    session = params["session"] if "session" in params else getattr(settings, "session_id", None)
+    key = (session, params["peer"])
+    want = (params.get("k"), params.get("ratio"), layout_of(model)._signature)
+    with _sharers_lock:
+        entry = _sharers.get(key)
+        if entry is None or entry[0] != want:
+            entry = _sharers[key] = (want, TopKSharer(model, k=want[0], ratio=want[1]), threading.Lock())
+    with entry[2]:
+        return [entry[1].share(model)]
+
+
+def aggregate_sparse(settings, params: Dict) -> List[nn.Module]:
+    """New: params {"model", "sparse_models", optional "weights"} -> [nn.Module],
+    the peer's own model averaged with its neighbours' sparse models, each
+    counting as the peer's own value where it stayed silent; weights as
+    `aggregate`'s, the own model's first."""
+    from dasklearn_amd.sparse import mix
+    model = params["model"]
+    if isinstance(model, tuple):
+        model = model[0]
+    return [mix(model, params["sparse_models"], params["weights"] if "weights" in params else None)]
 
 
 def chunk(settings, params: Dict) -> List:

@@ -1050,6 +1050,130 @@ int dlsim_wreduce_dist_batched(int b, const int* fan_in, const int* n_tensors, c
 int dlsim_reducedist_batch_geometry(int n, int dtype, int* max_segments, int* max_ptrs);
 
 /*
+ * dlsim_topk_select: top-k sparsified sharing, the sender's half. Of a flat
+ * model d_x it selects the k coordinates that moved most since they were last
+ * shared (CHOCO-SGD and partial-model sharing).
+ *
+ * New, no reference code: the reference shares dense models only
+ * (dasklearn/functions.py:89-106 receives whole modules).
+ *   d[e]   = float(d_x[e]) - float(d_ref[e]): one fp32 subtraction (bf16
+ *            widens exactly)
+ *   key[e] = the bit pattern of d[e] with the sign bit cleared, compared as an
+ *            unsigned integer
+ * Under this key the order is |d|, then +Inf, then NaN: a NaN delta ranks
+ * highest and is always shared, which is what torch.topk does. +0 and -0 both
+ * give key 0. Selected are the k elements with the largest keys; among equal
+ * keys at the threshold the lowest indices win.
+ *   d_x          the model, n_elems elements of dtype; only read
+ *   d_ref        the last-shared copy, n_elems elements; updated in place with
+ *                d_ref[d_idx[i]] = d_x[d_idx[i]], every other byte unchanged
+ *   k            0 <= k <= n_elems < 2^31; k == 0 (and so n_elems == 0)
+ *                launches nothing, k == n_elems selects everything
+ *   dtype        DLSIM_F32 or DLSIM_BF16 (anything else: DLSIM_E_DTYPE)
+ *   d_idx        k int32 indices, strictly ascending
+ *   d_val        k elements of dtype, d_val[i] = d_x[d_idx[i]], a bit copy
+ *   d_threshold  NULL, or a device uint32 that receives the threshold key (the
+ *                smallest selected key)
+ * The result is a function of the arguments alone: three radix passes on the
+ * key (11 + 10 + 10 bits) with integer histogram adds, a count per block
+ * scanned in block order, and a compaction in element order; no float atomics.
+ * The workspace is the call's own (hipMallocAsync / hipFreeAsync on `stream`),
+ * so calls on several streams and threads do not meet. No two of d_x, d_ref,
+ * d_idx, d_val and d_threshold may share a byte. Any alignment is accepted:
+ * 16-byte-aligned d_x and d_ref take the vector form, anything else a scalar
+ * form. Argument errors are decided before any HIP call. Stream-ordered.
+ */
+int dlsim_topk_select(const void* d_x, void* d_ref, size_t n_elems, long long k, int dtype, int32_t* d_idx, void* d_val,
+                      uint32_t* d_threshold, void* stream);
+
+/*
+ * dlsim_topk_geometry: the launch shape of dlsim_topk_select for n_elems
+ * elements of dtype, for tests that aim at its edges. vec_tile_elems: one
+ * 16-byte vector per lane of a block; block_tile_elems: a block's tile;
+ * max_blocks: the grid's cap (past max_blocks * block_tile_elems elements a
+ * block takes several consecutive tiles); blocks and workspace_bytes: of this
+ * call. Host only. (New: no reference counterpart.)
+ */
+int dlsim_topk_geometry(size_t n_elems, int dtype, size_t* vec_tile_elems, size_t* block_tile_elems,
+                        unsigned* max_blocks, unsigned* blocks, size_t* workspace_bytes);
+
+/*
+ * dlsim_topk_kernel_name: the writing kernel and the form ("<vec>" or
+ * "<scalar>") dlsim_topk_select runs for these arguments, "" for no launch or
+ * bad arguments; the sibling of dlsim_kernel_name. Host only.
+ */
+const char* dlsim_topk_kernel_name(const void* d_x, const void* d_ref, size_t n_elems, long long k, int dtype);
+
+/*
+ * dlsim_sparse_wreduce: top-k sparsified sharing, the receiver's half. The
+ * weighted mix of one dense row with m sparse neighbours, each of which counts
+ * as the receiver's own value wherever it stayed silent.
+ *
+ * New, no reference code: the reference shares dense models only.
+ *   d_out[e] = the bits dlsim_wreduce gives in DLSIM_EXACT mode over the
+ *              n = m + 1 rows row_0 = d_self and row_j[e] = d_val[j-1][p] where
+ *              d_idx[j-1][p] == e, d_self[e] where e is absent: x0 * 0, then
+ *              acc = fl(acc + fl(w_i * x_i)) in input order, with the per-step
+ *              rounding of bf16
+ *   d_self     n_elems elements of dtype, n_elems < 2^31
+ *   m          0 <= m <= DLSIM_MAX_SPARSE_NEIGHBOURS
+ *   d_idx      host array of m device pointers: k[j] int32 indices each,
+ *              strictly ascending, in [0, n_elems): dlsim_topk_select's format
+ *   d_val      host array of m device pointers: k[j] elements of dtype each
+ *   k          host array of m counts, 0 <= k[j] <= n_elems (checked)
+ *   h_weights  host array of m + 1 fp32 weights, d_self's first
+ *   d_out      n_elems elements. It may BE d_self; any other overlap with
+ *              d_self, and any with a list, is DLSIM_E_ARG
+ *   dtype      DLSIM_F32 or DLSIM_BF16
+ * Order and range of the indices are the caller's promise. An index is used
+ * only after it was found inside the tile of coordinates a block holds, so a
+ * value outside [0, n_elems) is never dereferenced and nothing outside d_out
+ * is written; with lists that break the promise the values of d_out are
+ * unspecified. Any alignment is accepted (16-byte-aligned d_self and d_out
+ * take the vector form). Stream-ordered; no allocation.
+ */
+#define DLSIM_MAX_SPARSE_NEIGHBOURS 31
+int dlsim_sparse_wreduce(const void* d_self, int m, const int32_t* const* d_idx, const void* const* d_val,
+                         const long long* k, const float* h_weights, void* d_out, size_t n_elems, int dtype,
+                         void* stream);
+
+/*
+ * dlsim_sparse_wreduce_batched: b independent dlsim_sparse_wreduce tasks (one
+ * per peer of a simulated round) in a few launches; the sparse counterpart of
+ * dlsim_wreduce_batched. (New: it replaces no reference code.)
+ *   d_self, m, d_out, n_elems   host arrays of b entries
+ *   d_idx, d_val, k             host arrays of sum(m) entries, task t's after
+ *                               task t-1's
+ *   h_weights                   host array of sum(m) + b weights, task by task,
+ *                               each task's dense row first
+ * Every task runs on the virtual grid of its own flat call and is bit-identical
+ * to it. A launch carries at most max_tasks tasks and max_neighbours lists
+ * (dlsim_sparse_geometry); vector-form and scalar-form tasks go in launches of
+ * their own; a task without an element launches nothing; b == 0 is a no-op.
+ * The launches run their tasks concurrently: an output may share bytes with
+ * nothing the call reads or writes but its own dense row (DLSIM_E_ARG, decided
+ * for the whole list before the first launch and before any HIP call).
+ */
+int dlsim_sparse_wreduce_batched(int b, const void* const* d_self, const int* m, const int32_t* const* d_idx,
+                                 const void* const* d_val, const long long* k, const float* h_weights,
+                                 void* const* d_out, const size_t* n_elems, int dtype, void* stream);
+
+/*
+ * dlsim_sparse_geometry: a block's tile of coordinates, the cap of a task's
+ * grid (past max_blocks * tile_elems elements a block takes several tiles), the
+ * blocks of a task of n_elems elements, and the limits of one batched launch.
+ * Host only. (New: no reference counterpart.)
+ */
+int dlsim_sparse_geometry(size_t n_elems, int dtype, size_t* tile_elems, unsigned* max_blocks, unsigned* blocks,
+                          int* max_tasks, int* max_neighbours);
+
+/*
+ * dlsim_sparse_kernel_name: the kernel and form ("<vec>" or "<scalar>")
+ * dlsim_sparse_wreduce runs for these buffers, "" for no launch. Host only.
+ */
+const char* dlsim_sparse_kernel_name(const void* d_self, const void* d_out, size_t n_elems, int dtype);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
