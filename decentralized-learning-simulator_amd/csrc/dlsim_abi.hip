@@ -338,6 +338,16 @@ hipError_t sparse_run(int b, const void* const* self, const int* m, const int32_
                       hipStream_t st);
 const char* sparse_kernel_name(bool vec);
 void sparse_batch_limits(int* max_tasks, int* max_slots);
+// block-quantised sharing (inst_quant.hip; the geometry is partials.hpp's)
+hipError_t quantize_run(const void* x, void* e, size_t nelem, int dtype, int bits, bool stoch, uint32_t seed, void* codes,
+                        float* scales, hipStream_t st);
+hipError_t dequantize_run(const void* codes, const float* scales, size_t nelem, int dtype, int bits, void* out,
+                          hipStream_t st);
+hipError_t quant_reduce_run(int b, const void* const* self, const int* m, const void* const* codes,
+                            const float* const* scales, const int* bits, const float* w, void* const* out,
+                            const size_t* nelem, int dtype, hipStream_t st);
+const char* quant_kernel_name(int op, bool vec);
+void quant_batch_limits(int* max_tasks, int* max_slots);
 
 // why each family stops at its DLSIM_MAX_*_INPUTS (check_fan_in, fanin_checks.hpp)
 constexpr const char* kRobustLimit = "the sorting network is held in registers";
@@ -1691,6 +1701,159 @@ int dlsim_sparse_geometry(size_t n_elems, int dtype, size_t* tile_elems, unsigne
 const char* dlsim_sparse_kernel_name(const void* d_self, const void* d_out, size_t n_elems, int dtype) {
   if ((dtype != DLSIM_F32 && dtype != DLSIM_BF16) || n_elems == 0) return "";
   return sparse_kernel_name(aligned16(d_self) && aligned16(d_out));
+}
+
+// ---- block-quantised sharing -----------------------------------------------------
+namespace {
+
+// dtype, bits and length of every quantised-sharing entry
+int check_quant_format(int dtype, int bits, size_t n_elems, const char* entry) {
+  const int rc = check_sharing_dtype(dtype, entry);
+  if (rc != DLSIM_OK) return rc;
+  if (bits != 4 && bits != 8) return fail(DLSIM_E_ARG, "bits must be 4 or 8 (got %d)", bits);
+  if (n_elems >= kSharingMaxElems)
+    return fail(DLSIM_E_ARG, "n_elems must be < 2^31 (got %zu): the kernels index elements in 32 bits", n_elems);
+  return DLSIM_OK;
+}
+
+size_t quant_code_bytes(size_t n_elems, int bits) { return bits == 8 ? n_elems : (n_elems + 1) / 2; }
+size_t quant_scale_bytes(size_t n_elems) { return (n_elems + DLSIM_QUANT_BLOCK - 1) / DLSIM_QUANT_BLOCK * sizeof(float); }
+
+}  // namespace
+
+int dlsim_quantize(const void* d_x, void* d_resid, size_t n_elems, int dtype, int bits, int rounding, uint32_t seed,
+                   void* d_codes, float* d_scales, void* stream) {
+  g_err.clear();
+  const int rc = check_quant_format(dtype, bits, n_elems, "dlsim_quantize");
+  if (rc != DLSIM_OK) return rc;
+  if (rounding != DLSIM_QUANT_NEAREST && rounding != DLSIM_QUANT_STOCHASTIC)
+    return fail(DLSIM_E_ARG, "unknown rounding %d (DLSIM_QUANT_NEAREST or DLSIM_QUANT_STOCHASTIC)", rounding);
+  if (n_elems == 0) return DLSIM_OK;  // nothing launched, no pointer read
+  if (!d_x) return fail(DLSIM_E_ARG, "null model pointer");
+  if (!d_codes || !d_scales) return fail(DLSIM_E_ARG, "null code or scale output pointer");
+  if (addr(d_scales) % sizeof(float)) return fail(DLSIM_E_ARG, "the scales must be 4-byte aligned");
+  const size_t bytes = n_elems * elem_bytes(dtype), cb = quant_code_bytes(n_elems, bits), sb = quant_scale_bytes(n_elems);
+  if (d_resid && ranges_meet(d_x, bytes, d_resid, bytes)) return fail(DLSIM_E_ARG, "the model overlaps the residual");
+  if (ranges_meet(d_x, bytes, d_codes, cb)) return fail(DLSIM_E_ARG, "the model overlaps the code output");
+  if (ranges_meet(d_x, bytes, d_scales, sb)) return fail(DLSIM_E_ARG, "the model overlaps the scale output");
+  if (d_resid && ranges_meet(d_resid, bytes, d_codes, cb)) return fail(DLSIM_E_ARG, "the residual overlaps the code output");
+  if (d_resid && ranges_meet(d_resid, bytes, d_scales, sb)) return fail(DLSIM_E_ARG, "the residual overlaps the scale output");
+  if (ranges_meet(d_codes, cb, d_scales, sb)) return fail(DLSIM_E_ARG, "the code output overlaps the scale output");
+  const hipError_t e = quantize_run(d_x, d_resid, n_elems, dtype, bits, rounding == DLSIM_QUANT_STOCHASTIC, seed, d_codes,
+                                    d_scales, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "quantise launch");
+}
+
+int dlsim_dequantize(const void* d_codes, const float* d_scales, size_t n_elems, int dtype, int bits, void* d_out,
+                     void* stream) {
+  g_err.clear();
+  const int rc = check_quant_format(dtype, bits, n_elems, "dlsim_dequantize");
+  if (rc != DLSIM_OK) return rc;
+  if (n_elems == 0) return DLSIM_OK;
+  if (!d_codes || !d_scales) return fail(DLSIM_E_ARG, "null code or scale pointer");
+  if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+  if (addr(d_scales) % sizeof(float)) return fail(DLSIM_E_ARG, "the scales must be 4-byte aligned");
+  const size_t bytes = n_elems * elem_bytes(dtype);
+  if (ranges_meet(d_out, bytes, d_codes, quant_code_bytes(n_elems, bits)))
+    return fail(DLSIM_E_ARG, "the output overlaps the codes");
+  if (ranges_meet(d_out, bytes, d_scales, quant_scale_bytes(n_elems))) return fail(DLSIM_E_ARG, "the output overlaps the scales");
+  const hipError_t e = dequantize_run(d_codes, d_scales, n_elems, dtype, bits, d_out, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "dequantise launch");
+}
+
+int dlsim_quant_wreduce_batched(int b, const void* const* d_self, const int* m, const void* const* d_codes,
+                                const float* const* d_scales, const int* bits, const float* h_weights,
+                                void* const* d_out, const size_t* n_elems, int dtype, void* stream) {
+  g_err.clear();
+  int rc = check_sharing_dtype(dtype, "dlsim_quant_wreduce");
+  if (rc != DLSIM_OK) return rc;
+  if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
+  if (b == 0) return DLSIM_OK;
+  if (!d_self || !m || !h_weights || !d_out || !n_elems) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t esz = elem_bytes(dtype);
+  struct Rd {  // a range some task reads: its dense row (task >= 0) or a code or scale buffer (-1 - task)
+    uintptr_t a, b;
+    int task;
+  };
+  std::vector<Rd> reads;
+  std::vector<Span> writes;
+  size_t slot = 0;
+  for (int t = 0; t < b; ++t) {
+    if (m[t] < 0 || m[t] > DLSIM_MAX_QUANT_NEIGHBOURS)
+      return fail(DLSIM_E_ARG, "task %d: m must satisfy 0 <= m <= %d (got %d)", t, DLSIM_MAX_QUANT_NEIGHBOURS, m[t]);
+    if (m[t] > 0 && (!d_codes || !d_scales || !bits)) return fail(DLSIM_E_ARG, "null array argument");
+    const size_t P = n_elems[t];
+    if (P >= kSharingMaxElems)
+      return fail(DLSIM_E_ARG, "task %d: n_elems must be < 2^31 (got %zu): the kernels index elements in 32 bits", t, P);
+    if (P && (!d_self[t] || !d_out[t])) return fail(DLSIM_E_ARG, "task %d: null dense row or output pointer", t);
+    if (P) {
+      const uintptr_t s0 = addr(d_self[t]), o0 = addr(d_out[t]);
+      if (s0 != o0 && s0 < o0 + P * esz && o0 < s0 + P * esz)
+        return fail(DLSIM_E_ARG, "task %d: output partially overlaps the dense row", t);
+      reads.push_back({s0, s0 + P * esz, t});
+      writes.push_back({o0, o0 + P * esz, t});
+    }
+    for (int j = 0; j < m[t]; ++j, ++slot) {
+      if (bits[slot] != 4 && bits[slot] != 8)
+        return fail(DLSIM_E_ARG, "task %d, neighbour %d: bits must be 4 or 8 (got %d)", t, j, bits[slot]);
+      if (P == 0) continue;  // never read: any pointer will do
+      if (!d_codes[slot] || !d_scales[slot])
+        return fail(DLSIM_E_ARG, "task %d, neighbour %d: null code or scale pointer", t, j);
+      if (addr(d_scales[slot]) % sizeof(float))
+        return fail(DLSIM_E_ARG, "task %d, neighbour %d: the scales must be 4-byte aligned", t, j);
+      reads.push_back({addr(d_codes[slot]), addr(d_codes[slot]) + quant_code_bytes(P, bits[slot]), -1 - t});
+      reads.push_back({addr(d_scales[slot]), addr(d_scales[slot]) + quant_scale_bytes(P), -1 - t});
+    }
+  }
+  // one launch runs its tasks concurrently: an output shares bytes with nothing but its own dense row
+  std::sort(writes.begin(), writes.end(), [](const Span& x, const Span& y) { return x.a < y.a; });
+  for (size_t i = 1; i < writes.size(); ++i)
+    if (writes[i].a < writes[i - 1].b)
+      return fail(DLSIM_E_ARG, "the outputs of tasks %d and %d overlap", writes[i - 1].task, writes[i].task);
+  for (const Rd& r : reads) {
+    auto it = std::upper_bound(writes.begin(), writes.end(), r.a, [](uintptr_t v, const Span& x) { return v < x.b; });
+    for (; it != writes.end() && it->a < r.b; ++it) {
+      if (r.task == it->task) continue;  // a task's own dense row (exact or no overlap: checked above)
+      if (r.task < 0)
+        return fail(DLSIM_E_ARG, "the output of task %d overlaps the codes or scales of task %d", it->task, -1 - r.task);
+      return fail(DLSIM_E_ARG, "the output of task %d overlaps the dense row of task %d", it->task, r.task);
+    }
+  }
+  const hipError_t e = quant_reduce_run(b, d_self, m, d_codes, d_scales, bits, h_weights, d_out, n_elems, dtype,
+                                        static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "quantised reduce launch");
+}
+
+int dlsim_quant_wreduce(const void* d_self, int m, const void* const* d_codes, const float* const* d_scales,
+                        const int* bits, const float* h_weights, void* d_out, size_t n_elems, int dtype, void* stream) {
+  return dlsim_quant_wreduce_batched(1, &d_self, &m, d_codes, d_scales, bits, h_weights, &d_out, &n_elems, dtype, stream);
+}
+
+int dlsim_quant_geometry(size_t n_elems, int dtype, int bits, dlsim_quant_geom* geom) {
+  g_err.clear();
+  const int rc = check_quant_format(dtype, bits, n_elems, "dlsim_quant_geometry");
+  if (rc != DLSIM_OK) return rc;
+  if (!geom) return fail(DLSIM_E_ARG, "null result pointer");
+  const QuantGeom g = quant_geometry(n_elems, dtype, bits);
+  geom->block_elems = g.block;
+  geom->code_bytes = g.code_bytes;
+  geom->n_scales = g.n_scales;
+  geom->tile_elems = g.tile;
+  geom->reduce_tile_elems = g.reduce_tile;
+  geom->max_blocks = g.max_blocks;
+  geom->blocks = g.blocks;
+  geom->reduce_blocks = g.reduce_blocks;
+  quant_batch_limits(&geom->max_tasks, &geom->max_neighbours);
+  return DLSIM_OK;
+}
+
+const char* dlsim_quant_kernel_name(int op, const void* const* d_buffers, int n_buffers, size_t n_elems, int dtype) {
+  if ((dtype != DLSIM_F32 && dtype != DLSIM_BF16) || op < DLSIM_QUANT_OP_QUANTIZE || op > DLSIM_QUANT_OP_WREDUCE ||
+      n_elems == 0 || n_buffers < 0 || (n_buffers && !d_buffers))
+    return "";
+  bool vec = true;
+  for (int i = 0; i < n_buffers; ++i) vec = vec && aligned16(d_buffers[i]);
+  return quant_kernel_name(op, vec);
 }
 
 int dlsim_device_alloc(size_t nbytes, int flags, void** d_out, int* contiguous) {

@@ -84,6 +84,23 @@ struct SparseGeom {
 };
 SparseGeom sparse_geometry(size_t nelem, int dtype);
 
+// The grids and buffer sizes of block-quantised sharing (inst_quant.hip defines quant_geometry): the
+// quantiser's and the decoder's grid over tiles of one 16-byte vector per lane and row, and the virtual
+// grid of one quantised mixing task, which a batched launch gives every task unchanged.
+struct QuantGeom {
+  size_t block;            // elements of a quantisation block (one scale)
+  unsigned max_blocks;     // the cap of both grids
+  size_t tile;             // quantise / dequantise: elements of a tile
+  unsigned tpb;            // tiles per block
+  unsigned blocks;         // grid (0 for no element)
+  size_t reduce_tile;      // mixing: coordinates of a tile
+  unsigned reduce_tpb;     // consecutive tiles per block
+  unsigned reduce_blocks;  // grid (0 for no element)
+  size_t code_bytes;       // ceil(nelem * bits / 8)
+  size_t n_scales;         // ceil(nelem / block)
+};
+QuantGeom quant_geometry(size_t nelem, int dtype, int bits);
+
 inline unsigned finish_blocks(int items) {  // grid of a finish kernel: one wave per item (a pair, an input)
   return static_cast<unsigned>((items + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
 }

@@ -86,6 +86,12 @@ EXPORTS = (
     "dlsim_sparse_wreduce_batched",
     "dlsim_sparse_geometry",
     "dlsim_sparse_kernel_name",
+    "dlsim_quantize",
+    "dlsim_dequantize",
+    "dlsim_quant_wreduce",
+    "dlsim_quant_wreduce_batched",
+    "dlsim_quant_geometry",
+    "dlsim_quant_kernel_name",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -115,6 +121,14 @@ class ChunkLaunch(ctypes.Structure):
     """dlsim_chunk_launch (include/dlsim.h): one launch of a chunk-mean call."""
     _fields_ = [("form", ctypes.c_int), ("mf", ctypes.c_int), ("rows", ctypes.c_int), ("bpt", ctypes.c_int),
                 ("grid", ctypes.c_uint), ("ntasks", ctypes.c_int), ("first_task", ctypes.c_int)]
+
+
+class QuantGeom(ctypes.Structure):
+    """dlsim_quant_geom (include/dlsim.h): sizes, tiles and grids of block-quantised sharing."""
+    _fields_ = [("block_elems", ctypes.c_size_t), ("code_bytes", ctypes.c_size_t), ("n_scales", ctypes.c_size_t),
+                ("tile_elems", ctypes.c_size_t), ("reduce_tile_elems", ctypes.c_size_t),
+                ("max_blocks", ctypes.c_uint), ("blocks", ctypes.c_uint), ("reduce_blocks", ctypes.c_uint),
+                ("max_tasks", ctypes.c_int), ("max_neighbours", ctypes.c_int)]
 
 
 CHUNK_FORMS = ("tiled_few", "tiled", "table", "defer_rf4", "defer_rf8", "defer_m")  # DLSIM_CHUNK_*
@@ -290,6 +304,20 @@ def load() -> ctypes.CDLL:
         lib.dlsim_sparse_geometry.restype = i
         lib.dlsim_sparse_kernel_name.argtypes = [vp, vp, sz, i]
         lib.dlsim_sparse_kernel_name.restype = ctypes.c_char_p
+        fpp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i)
+        lib.dlsim_quantize.argtypes = [vp, vp, sz, i, i, i, ctypes.c_uint32, vp, vp, vp]
+        lib.dlsim_quantize.restype = i
+        lib.dlsim_dequantize.argtypes = [vp, vp, sz, i, i, vp, vp]
+        lib.dlsim_dequantize.restype = i
+        lib.dlsim_quant_wreduce.argtypes = [vp, i, ctypes.POINTER(vp), ctypes.POINTER(vp), ip, fpp, vp, sz, i, vp]
+        lib.dlsim_quant_wreduce.restype = i
+        lib.dlsim_quant_wreduce_batched.argtypes = [i, ctypes.POINTER(vp), ip, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                                    ip, fpp, ctypes.POINTER(vp), ctypes.POINTER(sz), i, vp]
+        lib.dlsim_quant_wreduce_batched.restype = i
+        lib.dlsim_quant_geometry.argtypes = [sz, i, i, ctypes.POINTER(QuantGeom)]
+        lib.dlsim_quant_geometry.restype = i
+        lib.dlsim_quant_kernel_name.argtypes = [i, ctypes.POINTER(vp), i, sz, i]
+        lib.dlsim_quant_kernel_name.restype = ctypes.c_char_p
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -810,6 +838,140 @@ def sparse_wreduce(own, lists, weights_f32, out, stream=None):
                                        (ctypes.c_longlong * max(m, 1))(*[ix.numel() for ix, _ in lists]),
                                        (ctypes.c_float * (m + 1))(*[float(v) for v in weights_f32]), out.data_ptr(),
                                        own.numel(), dt, _stream_handle(out.device, stream)))
+    return out
+
+
+# ---- block-quantised sharing: quantiser, decoder and the fused decode-reduce ----
+MAX_QUANT_NEIGHBOURS = 31  # include/dlsim.h DLSIM_MAX_QUANT_NEIGHBOURS
+QUANT_BLOCK = 256  # DLSIM_QUANT_BLOCK
+QUANT_ROUNDINGS = {"nearest": 0, "stochastic": 1}  # DLSIM_QUANT_NEAREST, DLSIM_QUANT_STOCHASTIC
+QUANT_OPS = {"quantize": 0, "dequantize": 1, "wreduce": 2}  # DLSIM_QUANT_OP_*
+
+
+def mix32(h: int) -> int:
+    """The 32-bit mixer of the stochastic rounding (include/dlsim.h)."""
+    h &= 0xffffffff
+    h ^= h >> 16
+    h = h * 0x7feb352d & 0xffffffff
+    h ^= h >> 15
+    h = h * 0x846ca68b & 0xffffffff
+    return h ^ h >> 16
+
+
+def quant_geometry(numel: int, torch_dtype, bits: int = 8) -> dict:
+    """dlsim_quant_geometry as a dict of dlsim_quant_geom's fields."""
+    g = QuantGeom()
+    _check("dlsim_quant_geometry", load().dlsim_quant_geometry(numel, sharing_dtype_code(torch_dtype), bits, ctypes.byref(g)))
+    return {name: getattr(g, name) for name, _ in QuantGeom._fields_}
+
+
+def quant_kernel_name(op: str, buffers, numel: int, torch_dtype) -> str:
+    """dlsim_quant_kernel_name of op "quantize" / "dequantize" / "wreduce" for the tensors whose alignment decides."""
+    ptrs = [t.data_ptr() for t in buffers]
+    return load().dlsim_quant_kernel_name(QUANT_OPS[op], _ptr_array(ptrs), len(ptrs), numel,
+                                          sharing_dtype_code(torch_dtype)).decode()
+
+
+def check_quant_fan_in(m: int) -> None:
+    _check_fan_in(m + 1, MAX_QUANT_NEIGHBOURS + 1, "the quantised mixing kernel takes at most {limit} models, the "
+                                                   "receiver's own included (got {n})")
+
+
+def _check_quant_buffers(numel: int, bits: int, codes, scales, device) -> None:
+    import torch
+    if bits not in (4, 8):
+        raise ValueError(f"bits must be 4 or 8 (got {bits})")
+    if (codes.dtype != torch.uint8 or scales.dtype != torch.float32 or codes.numel() != (numel * bits + 7) // 8
+            or scales.numel() != (numel + QUANT_BLOCK - 1) // QUANT_BLOCK):
+        raise ValueError("a quantised row is ceil(numel * bits / 8) uint8 codes and ceil(numel / 256) float32 scales")
+    for t in (codes, scales):
+        if not t.is_cuda or t.device != device or not t.is_contiguous():
+            raise ValueError("quantised sharing needs contiguous device tensors on one device (no CPU path)")
+
+
+def quantize(x, codes, scales, bits: int = 8, rounding: str = "nearest", seed: int = 0, resid=None, stream=None):
+    """dlsim_quantize: the flat device tensor `x` (fp32 or bf16) as `codes`
+    (uint8, ceil(numel * bits / 8)) and `scales` (float32, one per 256
+    elements). `resid`: the error-feedback residual, x's dtype and size, read
+    and updated in place. Stream-ordered."""
+    dt = sharing_dtype_code(x.dtype)
+    _check_quant_buffers(x.numel(), bits, codes, scales, x.device)
+    for t in (x,) + (() if resid is None else (resid,)):
+        if not t.is_cuda or t.device != x.device or not t.is_contiguous() or t.dtype != x.dtype or t.numel() != x.numel():
+            raise ValueError("model and residual must be contiguous device tensors of one dtype, size and device")
+    _check("dlsim_quantize",
+           load().dlsim_quantize(x.data_ptr(), None if resid is None else resid.data_ptr(), x.numel(), dt, bits,
+                                 QUANT_ROUNDINGS[rounding], int(seed) & 0xffffffff, codes.data_ptr(), scales.data_ptr(),
+                                 _stream_handle(x.device, stream)))
+    return codes, scales
+
+
+def dequantize(codes, scales, bits: int, out, stream=None):
+    """dlsim_dequantize: the quantised row decoded into the flat device tensor `out` (fp32 or bf16)."""
+    dt = sharing_dtype_code(out.dtype)
+    if not out.is_cuda or not out.is_contiguous():
+        raise ValueError("quantised sharing needs contiguous device tensors on one device (no CPU path)")
+    _check_quant_buffers(out.numel(), bits, codes, scales, out.device)
+    _check("dlsim_dequantize",
+           load().dlsim_dequantize(codes.data_ptr(), scales.data_ptr(), out.numel(), dt, bits, out.data_ptr(),
+                                   _stream_handle(out.device, stream)))
+    return out
+
+
+def quant_wreduce_batched(tasks, stream=None):
+    """dlsim_quant_wreduce_batched over tasks (own, [(codes, scales, bits),
+    ...], weights_f32, out): flat device tensors of one dtype on one device;
+    weights own's first. out may be own. Stream-ordered; the tensors must
+    outlive the launches."""
+    if not tasks:
+        return
+    dev, tdt = tasks[0][3].device, tasks[0][0].dtype
+    dt = sharing_dtype_code(tdt)
+    selfs, ms, codes, scales, bits, ws, outs, ns = [], [], [], [], [], [], [], []
+    for own, rows, w, out in tasks:
+        check_quant_fan_in(len(rows))
+        if len(w) != len(rows) + 1:
+            raise AssertionError("weights/models length mismatch")
+        for t in (own, out):
+            if not t.is_cuda or t.device != dev or t.dtype != tdt or not t.is_contiguous() or t.numel() != own.numel():
+                raise ValueError("the quantised reduce needs contiguous device tensors of one dtype, size and device")
+        for cd, sc, nb in rows:
+            _check_quant_buffers(own.numel(), nb, cd, sc, dev)
+            codes.append(cd.data_ptr())
+            scales.append(sc.data_ptr())
+            bits.append(nb)
+        selfs.append(own.data_ptr())
+        outs.append(out.data_ptr())
+        ms.append(len(rows))
+        ns.append(own.numel())
+        ws += [float(v) for v in w]
+    b = len(tasks)
+    _check("dlsim_quant_wreduce_batched",
+           load().dlsim_quant_wreduce_batched(b, _ptr_array(selfs), (ctypes.c_int * b)(*ms), _ptr_array(codes),
+                                              _ptr_array(scales), (ctypes.c_int * max(len(bits), 1))(*bits),
+                                              (ctypes.c_float * len(ws))(*ws), _ptr_array(outs), _size_array(ns), dt,
+                                              _stream_handle(dev, stream)))
+
+
+def quant_wreduce(own, rows, weights_f32, out, stream=None):
+    """dlsim_quant_wreduce: out = the exact weighted reduce of `own` and the
+    quantised neighbours `rows` ([(codes, scales, bits), ...]), decoded on the fly."""
+    check_quant_fan_in(len(rows))
+    if len(weights_f32) != len(rows) + 1:
+        raise AssertionError("weights/models length mismatch")
+    dt = sharing_dtype_code(own.dtype)
+    for t in (own, out):
+        if not t.is_cuda or t.device != out.device or t.dtype != own.dtype or not t.is_contiguous() or t.numel() != own.numel():
+            raise ValueError("the quantised reduce needs contiguous device tensors of one dtype, size and device")
+    for cd, sc, nb in rows:
+        _check_quant_buffers(own.numel(), nb, cd, sc, out.device)
+    m = len(rows)
+    _check("dlsim_quant_wreduce",
+           load().dlsim_quant_wreduce(own.data_ptr(), m, _ptr_array([cd.data_ptr() for cd, _, _ in rows]),
+                                      _ptr_array([sc.data_ptr() for _, sc, _ in rows]),
+                                      (ctypes.c_int * max(m, 1))(*[nb for _, _, nb in rows]),
+                                      (ctypes.c_float * (m + 1))(*[float(v) for v in weights_f32]), out.data_ptr(),
+                                      own.numel(), dt, _stream_handle(out.device, stream)))
     return out
 
 

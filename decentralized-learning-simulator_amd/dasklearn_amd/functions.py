@@ -23,23 +23,43 @@ from dasklearn_amd.model_manager import ModelManager
 logger = logging.getLogger(__name__)
 
 __all__ = ["aggregate", "gradient_update", "chunk", "reconstruct_from_chunks", "sparsify", "aggregate_sparse",
-           "reset_sharers"]
+           "quantize", "aggregate_quantized", "reset_sharers"]
 
-# One TopKSharer per (session, peer), kept in the worker between tasks: the
-# last-shared copy is the state of top-k sharing (sparsify below). Guarded by
-# a lock (a worker may run tasks on several threads); reset_sharers() drops it.
+# One sharer per (session, peer, kind), kept in the worker between tasks: the
+# last-shared copy is the state of top-k sharing (sparsify below, kind "topk"),
+# the residual and the call count that of quantised sharing (quantize, kind
+# "quant"). Guarded by a lock (a worker may run tasks on several threads);
+# reset_sharers() drops both kinds.
 _sharers: Dict = {}
 _sharers_lock = threading.Lock()
 
 
 def reset_sharers(session=None) -> None:
-    """Forget the last-shared copies of `session` (params["session"] of the
-    sparsify tasks; None: of every session). A process that runs one
-    simulation after another under the same session key calls this between
-    them, or the next run would start from the previous run's copies."""
+    """Forget the sharers' state (last-shared copies, residuals, call counts)
+    of `session` (params["session"] of the sparsify and quantize tasks; None:
+    of every session). A process that runs one simulation after another under
+    the same session key calls this between them, or the next run would start
+    from the previous run's state."""
     with _sharers_lock:
         for key in [k for k in _sharers if session is None or k[0] == session]:
             del _sharers[key]
+
+
+def _shared(settings, params: Dict, kind: str, want, make):
+    """params["model"] (the first round's (model, 0) unwrapped) and the entry
+    (want, sharer, lock) of the peer's sharer of `kind`, made by make() when
+    the peer has none yet or its configuration `want` changed."""
+    model = params["model"]
+    if isinstance(model, tuple):  # the first round's (model, 0), functions.py:31-32
+        model = model[0]
+    session = params["session"] if "session" in params else getattr(settings, "session_id", None)
+    key = (session, params["peer"], kind)
+    want = want(model)
+    with _sharers_lock:
+        entry = _sharers.get(key)
+        if entry is None or entry[0] != want:
+            entry = _sharers[key] = (want, make(model, want), threading.Lock())
+    return model, entry
 
 # The reference builds the model to reconstruct into from its model zoo
 # (functions.py:144, dasklearn.models.create_model). Out of scope here, so it
@@ -108,18 +128,45 @@ def sparsify(settings, params: Dict) -> List:
     after the other."""
     from dasklearn_amd.arena import layout_of
     from dasklearn_amd.sparse import TopKSharer
-    model = params["model"]
-    if isinstance(model, tuple):  # the first round's (model, 0), functions.py:31-32
-        model = model[0]
-    session = params["session"] if "session" in params else getattr(settings, "session_id", None)
-    key = (session, params["peer"])
-    want = (params.get("k"), params.get("ratio"), layout_of(model)._signature)
-    with _sharers_lock:
-        entry = _sharers.get(key)
-        if entry is None or entry[0] != want:
-            entry = _sharers[key] = (want, TopKSharer(model, k=want[0], ratio=want[1]), threading.Lock())
+    model, entry = _shared(settings, params, "topk",
+                           lambda m: (params.get("k"), params.get("ratio"), layout_of(m)._signature),
+                           lambda m, want: TopKSharer(m, k=want[0], ratio=want[1]))
     with entry[2]:
         return [entry[1].share(model)]
+
+
+def quantize(settings, params: Dict) -> List:
+    """New: params {"model", "peer", optional "bits" (8), "rounding"
+    ("nearest"), "error_feedback" (False), "seed" (0), "session"} ->
+    [QuantModel], the peer's model as 8- or 4-bit codes with one scale per 256
+    elements (dasklearn_amd/quant.py). The worker keeps one QuantSharer per
+    (session, peer), as sparsify keeps its TopKSharer and under the same lock:
+    it holds the error-feedback residual and the count of shares that seeds
+    the stochastic rounding. A peer whose bits, rounding, error_feedback, seed
+    or parameter list changes starts over; reset_sharers() drops the state
+    between runs."""
+    from dasklearn_amd.arena import layout_of
+    from dasklearn_amd.quant import QuantSharer
+    model, entry = _shared(settings, params, "quant",
+                           lambda m: (params.get("bits", 8), params.get("rounding", "nearest"),
+                                      bool(params.get("error_feedback", False)), params.get("seed", 0),
+                                      layout_of(m)._signature),
+                           lambda m, want: QuantSharer(m, bits=want[0], rounding=want[1], error_feedback=want[2],
+                                                       seed=want[3]))
+    with entry[2]:
+        return [entry[1].share(model)]
+
+
+def aggregate_quantized(settings, params: Dict) -> List[nn.Module]:
+    """New: params {"model", "quant_models", optional "weights"} ->
+    [nn.Module], the peer's own model averaged with its neighbours' quantised
+    models, decoded on the fly; weights as `aggregate`'s, the own model's
+    first."""
+    from dasklearn_amd.quant import mix
+    model = params["model"]
+    if isinstance(model, tuple):
+        model = model[0]
+    return [mix(model, params["quant_models"], params["weights"] if "weights" in params else None)]
 
 
 def aggregate_sparse(settings, params: Dict) -> List[nn.Module]:

@@ -109,6 +109,27 @@ class ModelInputs:
         return _restride(out, self.layout) if self.staged else out
 
 
+def flat_groups(inputs: ModelInputs) -> Dict[torch.dtype, torch.Tensor]:
+    """The single model of `inputs` as one flat device tensor per non-empty
+    dtype group (the sharing kernels of sparse.py and quant.py take one flat
+    row). A device arena (arena.to_device_arena, any aggregate's result) is
+    read in place and a host model is the row ModelInputs staged. A plain
+    device model, whose parameters are separate tensors, costs one more dense
+    copy here, on every call: its group is concatenated into a fresh arena
+    (the pointer lists ModelInputs resolved for the *_tensors entries are not
+    used)."""
+    flats = {}
+    for dt, kind, data in inputs:
+        if kind == "flat":
+            flats[dt] = data[0]
+            continue
+        flat = arena_empty(inputs.layout.totals[dt], dt, inputs.dev)
+        torch.cat([inputs.all_params[0][k].detach().reshape(-1) for k in inputs.layout.groups[dt]], out=flat)
+        inputs.staged = True
+        flats[dt] = flat
+    return flats
+
+
 def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Optional[bool] = None) -> nn.Module:
     """The coordinate-wise order-statistic aggregate of `models` on the GPU
     (dlsim_robust_reduce): per parameter element the n models' values are

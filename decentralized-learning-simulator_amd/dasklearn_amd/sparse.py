@@ -18,7 +18,7 @@ from torch import nn
 from . import _native
 from .arena import arena_empty, layout_of
 from .batch import _resolve
-from .model_inputs import ModelInputs
+from .model_inputs import ModelInputs, flat_groups as _flat_groups
 
 
 def split_k(k: int, sizes: Sequence[int]) -> List[int]:
@@ -59,26 +59,6 @@ class SparseModel:
 
     def to(self, device) -> "SparseModel":
         return SparseModel({dt: (idx.to(device), val.to(device), size) for dt, (idx, val, size) in self.groups.items()})
-
-
-def _flat_groups(inputs: ModelInputs) -> Dict[torch.dtype, torch.Tensor]:
-    """The single model of `inputs` as one flat device tensor per non-empty
-    dtype group. A device arena (arena.to_device_arena, any aggregate's
-    result) is read in place and a host model is the row ModelInputs staged.
-    A plain device model, whose parameters are separate tensors, costs one
-    more dense copy here, on every call: its group is concatenated into a
-    fresh arena (the pointer lists ModelInputs resolved for the *_tensors
-    entries are not used: both kernels take one flat row)."""
-    flats = {}
-    for dt, kind, data in inputs:
-        if kind == "flat":
-            flats[dt] = data[0]
-            continue
-        flat = arena_empty(inputs.layout.totals[dt], dt, inputs.dev)
-        torch.cat([inputs.all_params[0][k].detach().reshape(-1) for k in inputs.layout.groups[dt]], out=flat)
-        inputs.staged = True
-        flats[dt] = flat
-    return flats
 
 
 class TopKSharer:

@@ -1174,6 +1174,128 @@ int dlsim_sparse_geometry(size_t n_elems, int dtype, size_t* tile_elems, unsigne
 const char* dlsim_sparse_kernel_name(const void* d_self, const void* d_out, size_t n_elems, int dtype);
 
 /*
+ * Block-quantised sharing: a flat row of n_elems elements (DLSIM_F32 or
+ * DLSIM_BF16, n_elems < 2^31) goes on the wire as one signed code per element
+ * and one fp32 scale per block of DLSIM_QUANT_BLOCK consecutive elements (the
+ * last block may be short). New, no reference code: the reference shares
+ * dense models only.
+ *   bits = 8: codes in [-127, 127], one int8 per element
+ *   bits = 4: codes in [-7, 7], two's-complement nibbles, the even element in
+ *             the low nibble; a last odd element leaves the high nibble 0
+ *   codes: ceil(n_elems * bits / 8) bytes; scales: ceil(n_elems / 256) floats
+ * The arithmetic, every operation one correctly rounded fp32 operation without
+ * contraction. Per block, t_i is the value to send (x_i widened to fp32; with
+ * a residual e, fl(x_i + e_i)), A the maximum of bits(t_i) & 0x7fffffff as
+ * unsigned integers, a = float(A):
+ *   A >= 0x7f800000 (an Inf or NaN in the block): scale = NaN, all codes 0: the
+ *                   block decodes to NaN throughout
+ *   a < 2^-96:      scale = +0, all codes 0: the block is sent as zeros
+ *   otherwise:      scale = fl(a / qmax), r = fl(qmax / a), y_i = fl(t_i * r),
+ *                   q_i = clamp(round(y_i), -qmax, qmax), with
+ *     DLSIM_QUANT_NEAREST:    round = rint, ties to even
+ *     DLSIM_QUANT_STOCHASTIC: round = floor(fl(y_i + u_i)), u_i = float(h_i >> 8)
+ *                   * 2^-24, h_i = mix32(i ^ mix32(seed)), i the element's index
+ *                   in the row; mix32(h): h ^= h >> 16; h *= 0x7feb352d;
+ *                   h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16 on uint32
+ * Decode: xhat_i = fl(float(q_i) * scale), for DLSIM_BF16 then rounded to bf16
+ * (ties to even), so a decoded row is a row of dtype.
+ *
+ * dlsim_quantize: d_x -> d_codes, d_scales. d_resid (or NULL) is the error-
+ * feedback residual, n_elems elements of dtype, read and then overwritten with
+ * e'_i = fl(t_i - xhat_i) rounded to dtype. In a block whose scale is NaN every
+ * e'_i is NaN: an Inf or NaN in the model poisons that block's residual for
+ * good, as it poisons the block on the wire. No buffer may overlap another
+ * (DLSIM_E_ARG); d_scales must be 4-byte aligned. 16-byte-aligned d_x, d_resid
+ * and d_codes take the vector form, anything else the scalar form.
+ * n_elems == 0 launches nothing and reads no pointer. Stream-ordered; no
+ * allocation.
+ */
+#define DLSIM_QUANT_BLOCK 256
+#define DLSIM_QUANT_NEAREST 0
+#define DLSIM_QUANT_STOCHASTIC 1
+int dlsim_quantize(const void* d_x, void* d_resid, size_t n_elems, int dtype, int bits, int rounding, uint32_t seed,
+                   void* d_codes, float* d_scales, void* stream);
+
+/*
+ * dlsim_dequantize: the plain decode of d_codes and d_scales into the dense
+ * row d_out (n_elems elements of dtype), which may overlap neither. Whatever
+ * the code bytes hold, nothing but d_out is written. 16-byte-aligned d_codes
+ * and d_out take the vector form.
+ */
+int dlsim_dequantize(const void* d_codes, const float* d_scales, size_t n_elems, int dtype, int bits, void* d_out,
+                     void* stream);
+
+/*
+ * dlsim_quant_wreduce: the receiver's mix. d_out[e] = the bits dlsim_wreduce
+ * gives in DLSIM_EXACT mode over the n = m + 1 rows row_0 = d_self and row_j =
+ * neighbour j decoded as dlsim_dequantize decodes it: x0 * 0, then acc =
+ * fl(acc + fl(w_i * x_i)) in input order, with the per-step rounding of bf16.
+ * No neighbour is materialised; a weight is never folded into a scale.
+ *   m          0 <= m <= DLSIM_MAX_QUANT_NEIGHBOURS
+ *   d_codes    host array of m device pointers to codes
+ *   d_scales   host array of m device pointers to scales (4-byte aligned)
+ *   bits       host array of m values, 4 or 8 each: neighbours may differ
+ *   h_weights  host array of m + 1 fp32 weights, d_self's first
+ *   d_out      n_elems elements. It may BE d_self; any other overlap with
+ *              d_self, and any with codes or scales, is DLSIM_E_ARG
+ * Nothing but d_out is written and nothing outside the code and scale buffers
+ * is read, whatever the codes hold. 16-byte-aligned d_self, d_out and code
+ * buffers take the vector form. Stream-ordered; no allocation.
+ */
+#define DLSIM_MAX_QUANT_NEIGHBOURS 31
+int dlsim_quant_wreduce(const void* d_self, int m, const void* const* d_codes, const float* const* d_scales,
+                        const int* bits, const float* h_weights, void* d_out, size_t n_elems, int dtype, void* stream);
+
+/*
+ * dlsim_quant_wreduce_batched: b independent dlsim_quant_wreduce tasks in a few
+ * launches, laid out as dlsim_sparse_wreduce_batched's arguments: d_self, m,
+ * d_out, n_elems have b entries; d_codes, d_scales, bits sum(m) entries, task
+ * t's after task t-1's; h_weights sum(m) + b weights, task by task, each
+ * task's dense row first. Every task runs on the virtual grid of its own flat
+ * call and is bit-identical to it. A launch carries at most max_tasks tasks and
+ * max_neighbours neighbours (dlsim_quant_geometry); vector-form and scalar-form
+ * tasks go in launches of their own; a task without an element launches
+ * nothing; b == 0 is a no-op. An output may share bytes with nothing the call
+ * reads or writes but its own dense row (DLSIM_E_ARG, decided for the whole
+ * list before any HIP call).
+ */
+int dlsim_quant_wreduce_batched(int b, const void* const* d_self, const int* m, const void* const* d_codes,
+                                const float* const* d_scales, const int* bits, const float* h_weights,
+                                void* const* d_out, const size_t* n_elems, int dtype, void* stream);
+
+/*
+ * dlsim_quant_geometry: the buffer sizes of a row of n_elems elements at
+ * `bits`, the tile and grid of dlsim_quantize / dlsim_dequantize, the tile and
+ * grid of a dlsim_quant_wreduce task (past max_blocks tiles a block takes
+ * several), and the limits of one batched launch. Host only.
+ */
+typedef struct dlsim_quant_geom {
+  size_t block_elems;       /* DLSIM_QUANT_BLOCK */
+  size_t code_bytes;        /* ceil(n_elems * bits / 8) */
+  size_t n_scales;          /* ceil(n_elems / block_elems) */
+  size_t tile_elems;        /* quantise and dequantise: elements of a tile */
+  size_t reduce_tile_elems; /* mixing: coordinates of a tile */
+  unsigned max_blocks;      /* the cap of every grid */
+  unsigned blocks;          /* quantise and dequantise grid */
+  unsigned reduce_blocks;   /* grid of one mixing task */
+  int max_tasks;            /* of one batched launch */
+  int max_neighbours;       /* of one batched launch, over its tasks */
+} dlsim_quant_geom;
+int dlsim_quant_geometry(size_t n_elems, int dtype, int bits, dlsim_quant_geom* geom);
+
+/*
+ * dlsim_quant_kernel_name: the kernel and form ("<vec>" or "<scalar>") that
+ * entry `op` runs when d_buffers are the buffers whose alignment decides it
+ * (quantise: d_x, d_resid if any, d_codes; dequantise: d_codes, d_out; mixing:
+ * d_self, d_out and every code buffer); "" for no launch or bad arguments.
+ * Host only.
+ */
+#define DLSIM_QUANT_OP_QUANTIZE 0
+#define DLSIM_QUANT_OP_DEQUANTIZE 1
+#define DLSIM_QUANT_OP_WREDUCE 2
+const char* dlsim_quant_kernel_name(int op, const void* const* d_buffers, int n_buffers, size_t n_elems, int dtype);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
