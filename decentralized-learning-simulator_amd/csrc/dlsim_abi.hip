@@ -348,6 +348,15 @@ hipError_t quant_reduce_run(int b, const void* const* self, const int* m, const 
                             const size_t* nelem, int dtype, hipStream_t st);
 const char* quant_kernel_name(int op, bool vec);
 void quant_batch_limits(int* max_tasks, int* max_slots);
+// MX sharing (inst_mx.hip; the geometry is partials.hpp's, the checks fanin_checks.hpp's)
+hipError_t mx_quantize_run(const void* x, void* e, size_t nelem, int dtype, int fmt, void* codes, void* scales,
+                           hipStream_t st);
+hipError_t mx_dequantize_run(const void* codes, const void* scales, size_t nelem, int dtype, int fmt, void* out,
+                             hipStream_t st);
+hipError_t mx_reduce_run(int b, const void* const* self, const int* m, const void* const* codes, const void* const* scales,
+                         const int* fmt, const float* w, void* const* out, const size_t* nelem, int dtype, hipStream_t st);
+const char* mx_kernel_name(int op, bool vec);
+void mx_batch_limits(int* max_tasks, int* max_slots);
 
 // why each family stops at its DLSIM_MAX_*_INPUTS (check_fan_in, fanin_checks.hpp)
 constexpr const char* kRobustLimit = "the sorting network is held in registers";
@@ -1854,6 +1863,95 @@ const char* dlsim_quant_kernel_name(int op, const void* const* d_buffers, int n_
   bool vec = true;
   for (int i = 0; i < n_buffers; ++i) vec = vec && aligned16(d_buffers[i]);
   return quant_kernel_name(op, vec);
+}
+
+// ---- MX sharing ----------------------------------------------------------------------
+int dlsim_mx_quantize(const void* d_x, void* d_resid, size_t n_elems, int dtype, int format, void* d_codes,
+                      void* d_scales, void* stream) {
+  g_err.clear();
+  int rc = check_mx_format(dtype, format, n_elems, "dlsim_mx_quantize");
+  if (rc != DLSIM_OK) return rc;
+  if (n_elems == 0) return DLSIM_OK;  // nothing launched, no pointer read
+  if (!d_x) return fail(DLSIM_E_ARG, "null model pointer");
+  if (!d_codes || !d_scales) return fail(DLSIM_E_ARG, "null code or scale output pointer");
+  const size_t bytes = n_elems * elem_bytes(dtype);
+  const NamedRange r[4] = {{"model", d_x, bytes},
+                           {"residual", d_resid, d_resid ? bytes : 0},
+                           {"code output", d_codes, mx_code_bytes(n_elems, format)},
+                           {"scale output", d_scales, mx_scale_bytes(n_elems)}};
+  rc = check_ranges_apart(r, 4);
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = mx_quantize_run(d_x, d_resid, n_elems, dtype, format, d_codes, d_scales, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "MX quantise launch");
+}
+
+int dlsim_mx_dequantize(const void* d_codes, const void* d_scales, size_t n_elems, int dtype, int format, void* d_out,
+                        void* stream) {
+  g_err.clear();
+  int rc = check_mx_format(dtype, format, n_elems, "dlsim_mx_dequantize");
+  if (rc != DLSIM_OK) return rc;
+  if (n_elems == 0) return DLSIM_OK;
+  if (!d_codes || !d_scales) return fail(DLSIM_E_ARG, "null code or scale pointer");
+  if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+  const NamedRange r[3] = {{"output", d_out, n_elems * elem_bytes(dtype)},
+                           {"codes", d_codes, mx_code_bytes(n_elems, format)},
+                           {"scales", d_scales, mx_scale_bytes(n_elems)}};
+  rc = check_ranges_apart(r, 2);  // the inputs may share bytes with each other
+  if (rc == DLSIM_OK) {
+    const NamedRange q[2] = {r[0], r[2]};
+    rc = check_ranges_apart(q, 2);
+  }
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = mx_dequantize_run(d_codes, d_scales, n_elems, dtype, format, d_out, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "MX dequantise launch");
+}
+
+int dlsim_mx_wreduce_batched(int b, const void* const* d_self, const int* m, const void* const* d_codes,
+                             const void* const* d_scales, const int* formats, const float* h_weights,
+                             void* const* d_out, const size_t* n_elems, int dtype, void* stream) {
+  g_err.clear();
+  int rc = check_mx_format(dtype, DLSIM_MX_FP8_E4M3, 0, "dlsim_mx_wreduce");
+  if (rc != DLSIM_OK) return rc;
+  if (b < 0) return fail(DLSIM_E_ARG, "b must be >= 0 (got %d)", b);
+  if (b == 0) return DLSIM_OK;
+  rc = check_mx_reduce_tasks(b, d_self, m, d_codes, d_scales, formats, h_weights, d_out, n_elems, elem_bytes(dtype),
+                             DLSIM_MAX_QUANT_NEIGHBOURS);
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = mx_reduce_run(b, d_self, m, d_codes, d_scales, formats, h_weights, d_out, n_elems, dtype,
+                                     static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "MX reduce launch");
+}
+
+int dlsim_mx_wreduce(const void* d_self, int m, const void* const* d_codes, const void* const* d_scales,
+                     const int* formats, const float* h_weights, void* d_out, size_t n_elems, int dtype, void* stream) {
+  return dlsim_mx_wreduce_batched(1, &d_self, &m, d_codes, d_scales, formats, h_weights, &d_out, &n_elems, dtype, stream);
+}
+
+int dlsim_mx_geometry(size_t n_elems, int dtype, int format, dlsim_mx_geom* geom) {
+  g_err.clear();
+  const int rc = check_mx_format(dtype, format, n_elems, "dlsim_mx_geometry");
+  if (rc != DLSIM_OK) return rc;
+  if (!geom) return fail(DLSIM_E_ARG, "null result pointer");
+  const MxGeom g = mx_geometry(n_elems, dtype, format);
+  geom->block_elems = g.block;
+  geom->code_bytes = g.code_bytes;
+  geom->scale_bytes = g.scale_bytes;
+  geom->tile_elems = g.tile;
+  geom->reduce_tile_elems = g.reduce_tile;
+  geom->max_blocks = g.max_blocks;
+  geom->blocks = g.blocks;
+  geom->reduce_blocks = g.reduce_blocks;
+  mx_batch_limits(&geom->max_tasks, &geom->max_neighbours);
+  return DLSIM_OK;
+}
+
+const char* dlsim_mx_kernel_name(int op, const void* const* d_buffers, int n_buffers, size_t n_elems, int dtype) {
+  if ((dtype != DLSIM_F32 && dtype != DLSIM_BF16) || op < DLSIM_QUANT_OP_QUANTIZE || op > DLSIM_QUANT_OP_WREDUCE ||
+      n_elems == 0 || n_buffers < 0 || (n_buffers && !d_buffers))
+    return "";
+  bool vec = true;
+  for (int i = 0; i < n_buffers; ++i) vec = vec && aligned16(d_buffers[i]);
+  return mx_kernel_name(op, vec);
 }
 
 int dlsim_device_alloc(size_t nbytes, int flags, void** d_out, int* contiguous) {

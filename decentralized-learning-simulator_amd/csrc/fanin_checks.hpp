@@ -222,6 +222,94 @@ inline int check_reducedist_tasks(int b, const int* fan_in, const int* n_tensors
   return DLSIM_OK;
 }
 
+// ---- MX sharing (dlsim_mx_*) ----
+inline size_t mx_code_bytes(size_t n_elems, int format) { return format == DLSIM_MX_FP4_E2M1 ? (n_elems + 1) / 2 : n_elems; }
+inline size_t mx_scale_bytes(size_t n_elems) { return (n_elems + DLSIM_MX_BLOCK - 1) / DLSIM_MX_BLOCK; }
+
+// dtype (DLSIM_E_DTYPE), format and length of every MX entry
+inline int check_mx_format(int dtype, int format, size_t n_elems, const char* entry) {
+  if (dtype != DLSIM_F32 && dtype != DLSIM_BF16)
+    return fail(DLSIM_E_DTYPE, "%s takes DLSIM_F32 and DLSIM_BF16 (got dtype %d): the dtypes of the shipped configurations",
+                entry, dtype);
+  if (format < DLSIM_MX_FP8_E4M3 || format > DLSIM_MX_FP4_E2M1)
+    return fail(DLSIM_E_ARG, "unknown format %d (DLSIM_MX_FP8_E4M3, DLSIM_MX_FP8_E5M2 or DLSIM_MX_FP4_E2M1)", format);
+  if (n_elems >> 31) return fail(DLSIM_E_ARG, "n_elems must be < 2^31 (got %zu): the kernels index elements in 32 bits", n_elems);
+  return DLSIM_OK;
+}
+
+// A buffer of one MX entry: its name in messages, its range. A null pointer with bytes == 0 is an absent buffer.
+struct NamedRange {
+  const char* name;
+  const void* p;
+  size_t bytes;
+};
+
+// no byte shared between any two of the k buffers, in the order given
+inline int check_ranges_apart(const NamedRange* r, int k) {
+  for (int i = 0; i < k; ++i)
+    for (int j = i + 1; j < k; ++j) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(r[i].p), b = reinterpret_cast<uintptr_t>(r[j].p);
+      if (r[i].bytes && r[j].bytes && a < b + r[j].bytes && b < a + r[i].bytes)
+        return fail(DLSIM_E_ARG, "the %s overlaps the %s", r[i].name, r[j].name);
+    }
+  return DLSIM_OK;
+}
+
+// The task list of dlsim_mx_wreduce_batched (b >= 1, the arrays laid out as dlsim_quant_wreduce_batched's): per
+// task, in order: 0 <= m <= max_m, n_elems < 2^31, non-null dense row and output that coincide or share nothing;
+// per neighbour a known format and, in a non-empty task, non-null codes and scales. Then the outputs against
+// each other and against everything any other task reads, and against their own task's codes and scales: one
+// launch runs its tasks concurrently.
+inline int check_mx_reduce_tasks(int b, const void* const* self, const int* m, const void* const* codes,
+                                 const void* const* scales, const int* formats, const float* w, void* const* outs,
+                                 const size_t* n_elems, size_t esz, int max_m) {
+  if (!self || !m || !w || !outs || !n_elems) return fail(DLSIM_E_ARG, "null array argument");
+  struct Rg {  // a range some task reads (its dense row: task >= 0; a code or scale buffer: -1 - task) or writes
+    uintptr_t a, b;
+    int task;
+  };
+  std::vector<Rg> reads, writes;
+  size_t slot = 0;
+  for (int t = 0; t < b; ++t) {
+    if (m[t] < 0 || m[t] > max_m) return fail(DLSIM_E_ARG, "task %d: m must satisfy 0 <= m <= %d (got %d)", t, max_m, m[t]);
+    if (m[t] > 0 && (!codes || !scales || !formats)) return fail(DLSIM_E_ARG, "null array argument");
+    const size_t P = n_elems[t];
+    if (P >> 31)
+      return fail(DLSIM_E_ARG, "task %d: n_elems must be < 2^31 (got %zu): the kernels index elements in 32 bits", t, P);
+    if (P && (!self[t] || !outs[t])) return fail(DLSIM_E_ARG, "task %d: null dense row or output pointer", t);
+    if (P) {
+      const uintptr_t s0 = reinterpret_cast<uintptr_t>(self[t]), o0 = reinterpret_cast<uintptr_t>(outs[t]);
+      if (s0 != o0 && s0 < o0 + P * esz && o0 < s0 + P * esz)
+        return fail(DLSIM_E_ARG, "task %d: output partially overlaps the dense row", t);
+      reads.push_back({s0, s0 + P * esz, t});
+      writes.push_back({o0, o0 + P * esz, t});
+    }
+    for (int j = 0; j < m[t]; ++j, ++slot) {
+      if (formats[slot] < DLSIM_MX_FP8_E4M3 || formats[slot] > DLSIM_MX_FP4_E2M1)
+        return fail(DLSIM_E_ARG, "task %d, neighbour %d: unknown format %d", t, j, formats[slot]);
+      if (P == 0) continue;  // never read: any pointer will do
+      if (!codes[slot] || !scales[slot]) return fail(DLSIM_E_ARG, "task %d, neighbour %d: null code or scale pointer", t, j);
+      const uintptr_t c0 = reinterpret_cast<uintptr_t>(codes[slot]), z0 = reinterpret_cast<uintptr_t>(scales[slot]);
+      reads.push_back({c0, c0 + mx_code_bytes(P, formats[slot]), -1 - t});
+      reads.push_back({z0, z0 + mx_scale_bytes(P), -1 - t});
+    }
+  }
+  std::sort(writes.begin(), writes.end(), [](const Rg& x, const Rg& y) { return x.a < y.a; });
+  for (size_t i = 1; i < writes.size(); ++i)
+    if (writes[i].a < writes[i - 1].b)
+      return fail(DLSIM_E_ARG, "the outputs of tasks %d and %d overlap", writes[i - 1].task, writes[i].task);
+  for (const Rg& r : reads) {
+    auto it = std::upper_bound(writes.begin(), writes.end(), r.a, [](uintptr_t v, const Rg& x) { return v < x.b; });
+    for (; it != writes.end() && it->a < r.b; ++it) {
+      if (r.task == it->task) continue;  // a task's own dense row (exact or no overlap: checked above)
+      if (r.task < 0)
+        return fail(DLSIM_E_ARG, "the output of task %d overlaps the codes or scales of task %d", it->task, -1 - r.task);
+      return fail(DLSIM_E_ARG, "the output of task %d overlaps the dense row of task %d", it->task, r.task);
+    }
+  }
+  return DLSIM_OK;
+}
+
 // row[i] = tensor k of model i, from the model-major in[i * t + k]
 inline void gather_row(const void* const* in, int n, int t, int k, const void** row) {
   for (int i = 0; i < n; ++i) row[i] = in[static_cast<size_t>(i) * static_cast<size_t>(t) + k];

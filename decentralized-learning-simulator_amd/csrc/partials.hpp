@@ -101,6 +101,21 @@ struct QuantGeom {
 };
 QuantGeom quant_geometry(size_t nelem, int dtype, int bits);
 
+// The same for MX sharing (inst_mx.hip defines mx_geometry): blocks of 32 elements, one scale byte each.
+struct MxGeom {
+  size_t block;            // elements of a block (one scale byte)
+  unsigned max_blocks;     // the cap of both grids
+  size_t tile;             // quantise / dequantise: elements of a tile
+  unsigned tpb;            // tiles per block
+  unsigned blocks;         // grid (0 for no element)
+  size_t reduce_tile;      // mixing: coordinates of a tile
+  unsigned reduce_tpb;     // consecutive tiles per block
+  unsigned reduce_blocks;  // grid (0 for no element)
+  size_t code_bytes;       // nelem (FP8) or ceil(nelem / 2) (FP4)
+  size_t scale_bytes;      // ceil(nelem / block)
+};
+MxGeom mx_geometry(size_t nelem, int dtype, int fmt);
+
 inline unsigned finish_blocks(int items) {  // grid of a finish kernel: one wave per item (a pair, an input)
   return static_cast<unsigned>((items + dlsim::kBlock / 64 - 1) / (dlsim::kBlock / 64));
 }

@@ -92,6 +92,12 @@ EXPORTS = (
     "dlsim_quant_wreduce_batched",
     "dlsim_quant_geometry",
     "dlsim_quant_kernel_name",
+    "dlsim_mx_quantize",
+    "dlsim_mx_dequantize",
+    "dlsim_mx_wreduce",
+    "dlsim_mx_wreduce_batched",
+    "dlsim_mx_geometry",
+    "dlsim_mx_kernel_name",
     "dlsim_device_alloc",
     "dlsim_device_free",
     "dlsim_pool_alloc",
@@ -126,6 +132,14 @@ class ChunkLaunch(ctypes.Structure):
 class QuantGeom(ctypes.Structure):
     """dlsim_quant_geom (include/dlsim.h): sizes, tiles and grids of block-quantised sharing."""
     _fields_ = [("block_elems", ctypes.c_size_t), ("code_bytes", ctypes.c_size_t), ("n_scales", ctypes.c_size_t),
+                ("tile_elems", ctypes.c_size_t), ("reduce_tile_elems", ctypes.c_size_t),
+                ("max_blocks", ctypes.c_uint), ("blocks", ctypes.c_uint), ("reduce_blocks", ctypes.c_uint),
+                ("max_tasks", ctypes.c_int), ("max_neighbours", ctypes.c_int)]
+
+
+class MxGeom(ctypes.Structure):
+    """dlsim_mx_geom (include/dlsim.h): sizes, tiles and grids of MX sharing."""
+    _fields_ = [("block_elems", ctypes.c_size_t), ("code_bytes", ctypes.c_size_t), ("scale_bytes", ctypes.c_size_t),
                 ("tile_elems", ctypes.c_size_t), ("reduce_tile_elems", ctypes.c_size_t),
                 ("max_blocks", ctypes.c_uint), ("blocks", ctypes.c_uint), ("reduce_blocks", ctypes.c_uint),
                 ("max_tasks", ctypes.c_int), ("max_neighbours", ctypes.c_int)]
@@ -318,6 +332,18 @@ def load() -> ctypes.CDLL:
         lib.dlsim_quant_geometry.restype = i
         lib.dlsim_quant_kernel_name.argtypes = [i, ctypes.POINTER(vp), i, sz, i]
         lib.dlsim_quant_kernel_name.restype = ctypes.c_char_p
+        lib.dlsim_mx_quantize.argtypes = [vp, vp, sz, i, i, vp, vp, vp]
+        lib.dlsim_mx_quantize.restype = i
+        lib.dlsim_mx_dequantize.argtypes = [vp, vp, sz, i, i, vp, vp]
+        lib.dlsim_mx_dequantize.restype = i
+        lib.dlsim_mx_wreduce.argtypes = lib.dlsim_quant_wreduce.argtypes
+        lib.dlsim_mx_wreduce.restype = i
+        lib.dlsim_mx_wreduce_batched.argtypes = lib.dlsim_quant_wreduce_batched.argtypes
+        lib.dlsim_mx_wreduce_batched.restype = i
+        lib.dlsim_mx_geometry.argtypes = [sz, i, i, ctypes.POINTER(MxGeom)]
+        lib.dlsim_mx_geometry.restype = i
+        lib.dlsim_mx_kernel_name.argtypes = [i, ctypes.POINTER(vp), i, sz, i]
+        lib.dlsim_mx_kernel_name.restype = ctypes.c_char_p
         lib.dlsim_device_alloc.argtypes = [sz, i, ctypes.POINTER(vp), ctypes.POINTER(i)]
         lib.dlsim_device_alloc.restype = i
         lib.dlsim_device_free.argtypes = [vp]
@@ -972,6 +998,128 @@ def quant_wreduce(own, rows, weights_f32, out, stream=None):
                                       (ctypes.c_int * max(m, 1))(*[nb for _, _, nb in rows]),
                                       (ctypes.c_float * (m + 1))(*[float(v) for v in weights_f32]), out.data_ptr(),
                                       own.numel(), dt, _stream_handle(out.device, stream)))
+    return out
+
+
+# ---- MX sharing: FP8 / FP4 codes with one power-of-two scale byte per 32 elements ----
+MX_BLOCK = 32  # DLSIM_MX_BLOCK
+MX_FORMATS = {"fp8_e4m3": 0, "fp8_e5m2": 1, "fp4": 2}  # DLSIM_MX_FP8_E4M3, DLSIM_MX_FP8_E5M2, DLSIM_MX_FP4_E2M1
+
+
+def mx_format_code(fmt: str) -> int:
+    if fmt not in MX_FORMATS:
+        raise ValueError(f'format must be "fp8_e4m3", "fp8_e5m2" or "fp4" (got {fmt!r})')
+    return MX_FORMATS[fmt]
+
+
+def mx_sizes(numel: int, fmt: str):
+    """(code bytes, scale bytes) of a row of numel elements."""
+    return ((numel + 1) // 2 if mx_format_code(fmt) == 2 else numel), (numel + MX_BLOCK - 1) // MX_BLOCK
+
+
+def mx_geometry(numel: int, torch_dtype, fmt: str = "fp8_e4m3") -> dict:
+    """dlsim_mx_geometry as a dict of dlsim_mx_geom's fields."""
+    g = MxGeom()
+    _check("dlsim_mx_geometry", load().dlsim_mx_geometry(numel, sharing_dtype_code(torch_dtype), mx_format_code(fmt), ctypes.byref(g)))
+    return {name: getattr(g, name) for name, _ in MxGeom._fields_}
+
+
+def mx_kernel_name(op: str, buffers, numel: int, torch_dtype) -> str:
+    """dlsim_mx_kernel_name of op "quantize" / "dequantize" / "wreduce" for the tensors whose alignment decides."""
+    ptrs = [t.data_ptr() for t in buffers]
+    return load().dlsim_mx_kernel_name(QUANT_OPS[op], _ptr_array(ptrs), len(ptrs), numel, sharing_dtype_code(torch_dtype)).decode()
+
+
+def _check_mx_buffers(numel: int, fmt: str, codes, scales, device) -> None:
+    import torch
+    if (codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or (codes.numel(), scales.numel()) != mx_sizes(numel, fmt)):
+        raise ValueError("an MX row is numel (FP8) or ceil(numel / 2) (FP4) uint8 codes and ceil(numel / 32) uint8 scales")
+    for t in (codes, scales):
+        if not t.is_cuda or t.device != device or not t.is_contiguous():
+            raise ValueError("MX sharing needs contiguous device tensors on one device (no CPU path)")
+
+
+def _check_mx_dense(ts, what: str) -> None:
+    for t in ts:
+        if not t.is_cuda or t.device != ts[0].device or not t.is_contiguous() or t.dtype != ts[0].dtype or t.numel() != ts[0].numel():
+            raise ValueError(f"{what} must be contiguous device tensors of one dtype, size and device")
+
+
+def mx_quantize(x, codes, scales, fmt: str = "fp8_e4m3", resid=None, stream=None):
+    """dlsim_mx_quantize: the flat device tensor `x` (fp32 or bf16) as `codes`
+    and `scales` (uint8, `mx_sizes`). `resid`: the error-feedback residual,
+    x's dtype and size, read and updated in place. Stream-ordered."""
+    dt = sharing_dtype_code(x.dtype)
+    _check_mx_buffers(x.numel(), fmt, codes, scales, x.device)
+    _check_mx_dense((x,) + (() if resid is None else (resid,)), "model and residual")
+    _check("dlsim_mx_quantize",
+           load().dlsim_mx_quantize(x.data_ptr(), None if resid is None else resid.data_ptr(), x.numel(), dt, MX_FORMATS[fmt],
+                                    codes.data_ptr(), scales.data_ptr(), _stream_handle(x.device, stream)))
+    return codes, scales
+
+
+def mx_dequantize(codes, scales, fmt: str, out, stream=None):
+    """dlsim_mx_dequantize: the MX row decoded into the flat device tensor `out` (fp32 or bf16)."""
+    dt = sharing_dtype_code(out.dtype)
+    _check_mx_dense((out,), "the output")
+    _check_mx_buffers(out.numel(), fmt, codes, scales, out.device)
+    _check("dlsim_mx_dequantize",
+           load().dlsim_mx_dequantize(codes.data_ptr(), scales.data_ptr(), out.numel(), dt, MX_FORMATS[fmt], out.data_ptr(),
+                                      _stream_handle(out.device, stream)))
+    return out
+
+
+def mx_wreduce_batched(tasks, stream=None):
+    """dlsim_mx_wreduce_batched over tasks (own, [(codes, scales, fmt), ...],
+    weights_f32, out): flat device tensors of one dtype on one device; weights
+    own's first. out may be own. Stream-ordered; the tensors must outlive the
+    launches."""
+    if not tasks:
+        return
+    dev = tasks[0][3].device
+    dt = sharing_dtype_code(tasks[0][0].dtype)
+    selfs, ms, codes, scales, fmts, ws, outs, ns = [], [], [], [], [], [], [], []
+    for own, rows, w, out in tasks:
+        check_quant_fan_in(len(rows))
+        if len(w) != len(rows) + 1:
+            raise AssertionError("weights/models length mismatch")
+        _check_mx_dense((own, out), "the MX reduce's rows")
+        if own.device != dev or own.dtype != tasks[0][0].dtype:
+            raise ValueError("the MX reduce's rows must be contiguous device tensors of one dtype, size and device")
+        for cd, sc, f in rows:
+            _check_mx_buffers(own.numel(), f, cd, sc, dev)
+            codes.append(cd.data_ptr())
+            scales.append(sc.data_ptr())
+            fmts.append(MX_FORMATS[f])
+        selfs.append(own.data_ptr())
+        outs.append(out.data_ptr())
+        ms.append(len(rows))
+        ns.append(own.numel())
+        ws += [float(v) for v in w]
+    b = len(tasks)
+    _check("dlsim_mx_wreduce_batched",
+           load().dlsim_mx_wreduce_batched(b, _ptr_array(selfs), (ctypes.c_int * b)(*ms), _ptr_array(codes), _ptr_array(scales),
+                                           (ctypes.c_int * max(len(fmts), 1))(*fmts), (ctypes.c_float * len(ws))(*ws),
+                                           _ptr_array(outs), _size_array(ns), dt, _stream_handle(dev, stream)))
+
+
+def mx_wreduce(own, rows, weights_f32, out, stream=None):
+    """dlsim_mx_wreduce: out = the exact weighted reduce of `own` and the MX
+    neighbours `rows` ([(codes, scales, fmt), ...]), decoded on the fly."""
+    check_quant_fan_in(len(rows))
+    if len(weights_f32) != len(rows) + 1:
+        raise AssertionError("weights/models length mismatch")
+    dt = sharing_dtype_code(own.dtype)
+    _check_mx_dense((out, own), "the MX reduce's rows")
+    for cd, sc, f in rows:
+        _check_mx_buffers(own.numel(), f, cd, sc, out.device)
+    m = len(rows)
+    _check("dlsim_mx_wreduce",
+           load().dlsim_mx_wreduce(own.data_ptr(), m, _ptr_array([cd.data_ptr() for cd, _, _ in rows]),
+                                   _ptr_array([sc.data_ptr() for _, sc, _ in rows]),
+                                   (ctypes.c_int * max(m, 1))(*[MX_FORMATS[f] for _, _, f in rows]),
+                                   (ctypes.c_float * (m + 1))(*[float(v) for v in weights_f32]), out.data_ptr(),
+                                   own.numel(), dt, _stream_handle(out.device, stream)))
     return out
 
 

@@ -28,8 +28,8 @@ __all__ = ["aggregate", "gradient_update", "chunk", "reconstruct_from_chunks", "
 # One sharer per (session, peer, kind), kept in the worker between tasks: the
 # last-shared copy is the state of top-k sharing (sparsify below, kind "topk"),
 # the residual and the call count that of quantised sharing (quantize, kind
-# "quant"). Guarded by a lock (a worker may run tasks on several threads);
-# reset_sharers() drops both kinds.
+# "quant", or "mx" when the task names an MX format). Guarded by a lock (a
+# worker may run tasks on several threads); reset_sharers() drops every kind.
 _sharers: Dict = {}
 _sharers_lock = threading.Lock()
 
@@ -144,9 +144,20 @@ def quantize(settings, params: Dict) -> List:
     it holds the error-feedback residual and the count of shares that seeds
     the stochastic rounding. A peer whose bits, rounding, error_feedback, seed
     or parameter list changes starts over; reset_sharers() drops the state
-    between runs."""
+    between runs. With params["format"] ("fp8_e4m3", "fp8_e5m2" or "fp4") the
+    result is an [MXModel] instead (dasklearn_amd/mx.py: MX codes, one scale
+    byte per 32 elements, nearest rounding; "bits", "rounding" and "seed" are
+    not read), from an MXSharer kept the same way."""
     from dasklearn_amd.arena import layout_of
     from dasklearn_amd.quant import QuantSharer
+    if "format" in params:
+        from dasklearn_amd.mx import MXSharer
+        model, entry = _shared(settings, params, "mx",
+                               lambda m: (params["format"], bool(params.get("error_feedback", False)),
+                                          layout_of(m)._signature),
+                               lambda m, want: MXSharer(m, fmt=want[0], error_feedback=want[1]))
+        with entry[2]:
+            return [entry[1].share(model)]
     model, entry = _shared(settings, params, "quant",
                            lambda m: (params.get("bits", 8), params.get("rounding", "nearest"),
                                       bool(params.get("error_feedback", False)), params.get("seed", 0),
@@ -161,11 +172,16 @@ def aggregate_quantized(settings, params: Dict) -> List[nn.Module]:
     """New: params {"model", "quant_models", optional "weights"} ->
     [nn.Module], the peer's own model averaged with its neighbours' quantised
     models, decoded on the fly; weights as `aggregate`'s, the own model's
-    first."""
-    from dasklearn_amd.quant import mix
+    first. The neighbours are all QuantModels or all MXModels (ValueError for
+    a list that mixes them: the two wire formats have a fused reduce each)."""
+    from dasklearn_amd import mx, quant
     model = params["model"]
     if isinstance(model, tuple):
         model = model[0]
+    kinds = {isinstance(qm, mx.MXModel) for qm in params["quant_models"]}
+    if len(kinds) > 1:
+        raise ValueError("aggregate_quantized takes integer-quantised or MX models, not a list that mixes them")
+    mix = mx.mix if kinds == {True} else quant.mix
     return [mix(model, params["quant_models"], params["weights"] if "weights" in params else None)]
 
 

@@ -1296,6 +1296,125 @@ int dlsim_quant_geometry(size_t n_elems, int dtype, int bits, dlsim_quant_geom* 
 const char* dlsim_quant_kernel_name(int op, const void* const* d_buffers, int n_buffers, size_t n_elems, int dtype);
 
 /*
+ * MX (OCP microscaling) sharing: a flat row of n_elems elements (DLSIM_F32 or
+ * DLSIM_BF16, n_elems < 2^31) goes on the wire as one element code per element
+ * and one scale byte S (E8M0: the power of two 2^(S-127)) per block of
+ * DLSIM_MX_BLOCK consecutive elements (the last block may be short). New, no
+ * reference code: the reference shares dense models only.
+ *   DLSIM_MX_FP8_E4M3: emax 8, max 448, one byte per element
+ *   DLSIM_MX_FP8_E5M2: emax 15, max 57344, one byte per element
+ *   DLSIM_MX_FP4_E2M1: emax 2, max 6, two elements per byte, the even element
+ *                      in the low nibble; a last odd element leaves the high
+ *                      nibble 0
+ *   codes: n_elems or ceil(n_elems / 2) bytes; scales: ceil(n_elems / 32) bytes
+ * Encode. Per block, t_i is the value to send (x_i widened to fp32; with a
+ * residual e, fl32(x_i + e_i)), A the maximum of bits(t_i) & 0x7fffffff as
+ * unsigned integers (dlsim_quantize's key):
+ *   A >= 0x7f800000 (an Inf or NaN in the block): S = 0xFF, every code 0
+ *   A <  0x1F800000 (largest magnitude below 2^-64): S = 0, every code 0. The
+ *                   threshold keeps every scale and every decoded value the
+ *                   quantiser can produce normal in fp32 (the smallest is
+ *                   E5M2's subnormal 2^-16 times 2^(48-127) = 2^-95)
+ *   otherwise:      S = (A >> 23) - emax, a value in [48, 252], and q_i encodes
+ *                   the real number t_i / 2^(S-127) in the element format:
+ *                   rounded to nearest, ties to the even code, the exponent
+ *                   taken as unbounded above, the format's subnormals included;
+ *                   then the magnitude clamped to the format's max (saturate,
+ *                   never Inf or NaN). The sign bit of the code is the sign bit
+ *                   of t_i, also for -0 and for values that round to zero
+ * Decode, defined for every byte value (the reduce may be handed foreign
+ * buffers): xhat_i = fl32(v(q_i) * 2^(S-127)) for S <= 254, one correctly
+ * rounded fp32 multiplication, fp32 subnormals included; v is the OCP value of
+ * the code (E4M3 S.1111.111 is NaN; E5M2 S.11111.00 is +-Inf, its other
+ * all-ones-exponent codes NaN); S = 0xFF makes every xhat_i of the block NaN.
+ * For DLSIM_BF16 the result is then rounded to bf16, ties to even: a no-op
+ * whenever the fp32 value is normal, an element having at most 3 mantissa
+ * bits. With S in [48, 252] every decoded value is exact in both dtypes.
+ * No stochastic rounding.
+ *
+ * dlsim_mx_quantize: d_x -> d_codes, d_scales. d_resid (or NULL) is the error-
+ * feedback residual, n_elems elements of dtype, read and then overwritten with
+ * e'_i = fl32(t_i - xhat_i) rounded to dtype: NaN throughout a block with
+ * S = 0xFF, t_i in an all-zero block. No buffer may overlap another
+ * (DLSIM_E_ARG). 16-byte-aligned d_x, d_resid and d_codes take the vector
+ * form, anything else the scalar form. n_elems == 0 launches nothing and reads
+ * no pointer. Stream-ordered; no allocation.
+ */
+#define DLSIM_MX_BLOCK 32
+#define DLSIM_MX_FP8_E4M3 0
+#define DLSIM_MX_FP8_E5M2 1
+#define DLSIM_MX_FP4_E2M1 2
+int dlsim_mx_quantize(const void* d_x, void* d_resid, size_t n_elems, int dtype, int format, void* d_codes,
+                      void* d_scales, void* stream);
+
+/*
+ * dlsim_mx_dequantize: the plain decode of d_codes and d_scales into the dense
+ * row d_out (n_elems elements of dtype), which may overlap neither. Whatever
+ * the bytes hold, nothing but d_out is written. 16-byte-aligned d_codes and
+ * d_out take the vector form.
+ */
+int dlsim_mx_dequantize(const void* d_codes, const void* d_scales, size_t n_elems, int dtype, int format, void* d_out,
+                        void* stream);
+
+/*
+ * dlsim_mx_wreduce: the receiver's mix, dlsim_quant_wreduce for MX neighbours.
+ * d_out[e] = the bits dlsim_wreduce gives in DLSIM_EXACT mode over the n = m + 1
+ * rows row_0 = d_self and row_j = neighbour j decoded as dlsim_mx_dequantize
+ * decodes it. No neighbour is materialised; a weight is never folded into a
+ * scale.
+ *   m          0 <= m <= DLSIM_MAX_QUANT_NEIGHBOURS
+ *   d_codes    host array of m device pointers to codes
+ *   d_scales   host array of m device pointers to scale bytes
+ *   formats    host array of m DLSIM_MX_* values: neighbours may differ
+ *   h_weights  host array of m + 1 fp32 weights, d_self's first
+ *   d_out      n_elems elements. It may BE d_self; any other overlap with
+ *              d_self, and any with codes or scales, is DLSIM_E_ARG
+ * Nothing but d_out is written and nothing outside the code and scale buffers
+ * is read, whatever they hold. 16-byte-aligned d_self, d_out and code buffers
+ * take the vector form. Stream-ordered; no allocation.
+ */
+int dlsim_mx_wreduce(const void* d_self, int m, const void* const* d_codes, const void* const* d_scales,
+                     const int* formats, const float* h_weights, void* d_out, size_t n_elems, int dtype, void* stream);
+
+/*
+ * dlsim_mx_wreduce_batched: b independent dlsim_mx_wreduce tasks in a few
+ * launches; arguments, launch limits, forms and overlap rules are
+ * dlsim_quant_wreduce_batched's, with formats in place of bits. Every task runs
+ * on the virtual grid of its own flat call and is bit-identical to it.
+ */
+int dlsim_mx_wreduce_batched(int b, const void* const* d_self, const int* m, const void* const* d_codes,
+                             const void* const* d_scales, const int* formats, const float* h_weights,
+                             void* const* d_out, const size_t* n_elems, int dtype, void* stream);
+
+/*
+ * dlsim_mx_geometry: dlsim_quant_geometry for MX sharing: the buffer sizes of a
+ * row of n_elems elements in `format`, the tile and grid of dlsim_mx_quantize /
+ * dlsim_mx_dequantize, the tile and grid of a dlsim_mx_wreduce task (past
+ * max_blocks tiles a block takes several), the limits of one batched launch.
+ * Host only.
+ */
+typedef struct dlsim_mx_geom {
+  size_t block_elems;       /* DLSIM_MX_BLOCK */
+  size_t code_bytes;        /* n_elems (FP8) or ceil(n_elems / 2) (FP4) */
+  size_t scale_bytes;       /* ceil(n_elems / block_elems) */
+  size_t tile_elems;        /* quantise and dequantise: elements of a tile */
+  size_t reduce_tile_elems; /* mixing: coordinates of a tile */
+  unsigned max_blocks;      /* the cap of every grid */
+  unsigned blocks;          /* quantise and dequantise grid */
+  unsigned reduce_blocks;   /* grid of one mixing task */
+  int max_tasks;            /* of one batched launch */
+  int max_neighbours;       /* of one batched launch, over its tasks */
+} dlsim_mx_geom;
+int dlsim_mx_geometry(size_t n_elems, int dtype, int format, dlsim_mx_geom* geom);
+
+/*
+ * dlsim_mx_kernel_name: dlsim_quant_kernel_name for the MX entries (op one of
+ * DLSIM_QUANT_OP_*; the same buffers decide); "" for no launch or bad
+ * arguments. Host only.
+ */
+const char* dlsim_mx_kernel_name(int op, const void* const* d_buffers, int n_buffers, size_t n_elems, int dtype);
+
+/*
  * dlsim_device_alloc / dlsim_device_free — device memory for long-lived
  * large buffers (staging rows, resident model blocks) on the calling
  * thread's current device. flags DLSIM_ALLOC_CONTIGUOUS asks the driver for
