@@ -72,6 +72,9 @@ EXPORTS = (
     "dlsim_pairwise_sqdist",
     "dlsim_pairwise_sqdist_tensors",
     "dlsim_pairdist_geometry",
+    "dlsim_gram_sqdist",
+    "dlsim_gram_sqdist_tensors",
+    "dlsim_gramdist_geometry",
     "dlsim_pairwise_sqdist_batched",
     "dlsim_pairdist_batch_geometry",
     "dlsim_wreduce_dist_batched",
@@ -280,6 +283,12 @@ def load() -> ctypes.CDLL:
         lib.dlsim_pairwise_sqdist_tensors.restype = i
         lib.dlsim_pairdist_geometry.argtypes = [i, i, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint)]
         lib.dlsim_pairdist_geometry.restype = i
+        lib.dlsim_gram_sqdist.argtypes = lib.dlsim_pairwise_sqdist.argtypes
+        lib.dlsim_gram_sqdist.restype = i
+        lib.dlsim_gram_sqdist_tensors.argtypes = lib.dlsim_pairwise_sqdist_tensors.argtypes
+        lib.dlsim_gram_sqdist_tensors.restype = i
+        lib.dlsim_gramdist_geometry.argtypes = lib.dlsim_pairdist_geometry.argtypes
+        lib.dlsim_gramdist_geometry.restype = i
         lib.dlsim_pairwise_sqdist_batched.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(vp),
                                                       ctypes.POINTER(sz), i, ctypes.POINTER(vp), i, vp]
         lib.dlsim_pairwise_sqdist_batched.restype = i
@@ -1222,6 +1231,42 @@ def pairdist_geometry(n: int, torch_dtype, numel: int):
     """(tile elements, blocks) of dlsim_pairwise_sqdist for n 16-byte-aligned
     inputs of numel elements (dlsim_pairdist_geometry; no GPU needed)."""
     return _geometry("dlsim_pairdist_geometry", n, torch_dtype, numel)
+
+
+def gram_sqdist(inputs, out, accumulate: bool = False, stream=None):
+    """dlsim_gram_sqdist: the matrix of pairwise_sqdist through the Gram matrix
+    of the rows centred on inputs[0], on the fp64 matrix unit: every row is
+    read once at any n <= 32. fp32, bf16 and fp16 (fp64: NativeError, use
+    pairwise_sqdist). A finite entry is within 2 (numel + 16) 2^-53 (S_i + S_j)
+    of the exact distance, S_i the squared distance of row i to row 0; an entry
+    of a row with a NaN or infinite element is NaN. Arguments, exceptions and
+    determinism as pairwise_sqdist."""
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_pairdist_fan_in(n)
+    _check_distances(out, n * n, "matrix")
+    dt, numel = _check_flat_inputs(inputs, None, out.device, "Gram distance")
+    _check("dlsim_gram_sqdist",
+           load().dlsim_gram_sqdist(_ptr_array([t.data_ptr() for t in inputs]), n, numel,
+                                    dtype_code(dt, single_task=True), out.data_ptr(), int(bool(accumulate)),
+                                    _stream_handle(out.device, stream)))
+    return out
+
+
+def gram_sqdist_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], dtype: int, out_ptr: int,
+                            accumulate: bool, stream_handle) -> None:
+    """dlsim_gram_sqdist_tensors, as pairwise_sqdist_tensors_raw."""
+    check_pairdist_fan_in(n)
+    _check("dlsim_gram_sqdist_tensors",
+           load().dlsim_gram_sqdist_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels), dtype,
+                                            out_ptr, int(bool(accumulate)), stream_handle))
+
+
+def gramdist_geometry(n: int, torch_dtype, numel: int):
+    """(tile elements, blocks) of dlsim_gram_sqdist for n 16-byte-aligned
+    inputs of numel elements (dlsim_gramdist_geometry; no GPU needed)."""
+    return _geometry("dlsim_gramdist_geometry", n, torch_dtype, numel)
 
 
 def pairwise_sqdist_batched_raw(fan_in: Sequence[int], n_tensors: Sequence[int], in_ptrs: Sequence[int],

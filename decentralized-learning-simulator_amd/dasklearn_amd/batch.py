@@ -85,9 +85,10 @@ def method_plugin(method, settings):
 def krum_rule(plugin):
     """(name, f, m) when `plugin` is a Krum or MultiKrum class (a subclass
     too: with_params makes one), else None. m: None for Krum, for Multi-Krum
-    the class's m or, by default, the function fan-in -> n - f."""
+    the class's m or, by default, the function fan-in -> n - f. A class whose
+    distance is not "exact" has no batched form (None: it runs per task)."""
     from .gradient_aggregation.krum import Krum, MultiKrum
-    if not isinstance(plugin, type):
+    if not isinstance(plugin, type) or getattr(plugin, "distance", "exact") != "exact":
         return None
     if issubclass(plugin, Krum):
         return "Krum", plugin.f, None

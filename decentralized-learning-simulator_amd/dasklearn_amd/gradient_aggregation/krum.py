@@ -41,6 +41,13 @@ matrix comes from batched launches (csrc/pairdist_batch_kernels.hpp, DESIGN.md
 serve the whole wave, and the copies or reduces that follow are batched too
 (`model_inputs.krum_arena_tasks`). `model_distances_batch` is that first phase
 on its own. A device-side selection is not implemented.
+
+`with_params(..., distance="gram")` (and `model_distances(method="gram")`)
+take the matrix from the Gram kernel instead (csrc/gramdist_kernels.hpp,
+DESIGN.md §8u): every model read once at any n, an error bound relative to the
+models' distances to models[0], NaN for both non-finite classes (which the rule
+above maps to +Inf alike). Such a plugin's aggregates of a round run task by
+task. The default everywhere is "exact".
 """
 import math
 from typing import List, Optional, Sequence
@@ -52,8 +59,8 @@ from dasklearn_amd import _native
 from dasklearn_amd.arena import _target_device, input_arenas
 from dasklearn_amd.gradient_aggregation import GradientAggregation
 from dasklearn_amd.gradient_aggregation.robust import _check_unweighted
-from dasklearn_amd.model_inputs import (bulyan_modules, distances_arena_tasks, krum_modules,  # noqa: F401
-                                        model_distances)  # (model_distances: public here)
+from dasklearn_amd.model_inputs import (bulyan_modules, check_distance_method, distances_arena_tasks,  # noqa: F401
+                                        krum_modules, model_distances)  # (model_distances: public here)
 from dasklearn_amd.wave_tasks import ArenaTask
 
 
@@ -187,6 +194,7 @@ class Krum(GradientAggregation):
     peers are tolerated among n >= 2f + 3."""
 
     f = 1
+    distance = "exact"
 
     @classmethod
     def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
@@ -194,18 +202,19 @@ class Krum(GradientAggregation):
         """to_host=None (default): the result lives where models[0] lives;
         False keeps it on the GPU."""
         _check_unweighted("Krum", models, weights)
-        return krum_modules(models, cls.f, None, to_host=to_host)
+        return krum_modules(models, cls.f, None, to_host=to_host, distance=cls.distance)
 
     @classmethod
-    def with_params(cls, f: int, m: Optional[int] = None):
+    def with_params(cls, f: int, m: Optional[int] = None, distance: str = "exact"):
         """A Krum class for Byzantine count f: the plugin signature
-        ModelManager calls. m is accepted for symmetry and must be None or 1."""
+        ModelManager calls. m is accepted for symmetry and must be None or 1.
+        distance: "exact" or "gram" (model_distances' method)."""
         f = int(f)
         if f < 0:
             raise ValueError(f"f must be >= 0 (got {f})")
         if m is not None and int(m) != 1:
             raise ValueError(f"Krum selects one model (got m = {m}); MultiKrum takes m")
-        return type(f"Krum{f}", (cls,), {"f": f})
+        return type(f"Krum{f}", (cls,), {"f": f, "distance": check_distance_method(distance)})
 
 
 class MultiKrum(GradientAggregation):
@@ -213,6 +222,7 @@ class MultiKrum(GradientAggregation):
 
     f = 1
     m: Optional[int] = None
+    distance = "exact"
 
     @classmethod
     def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
@@ -220,12 +230,12 @@ class MultiKrum(GradientAggregation):
         _check_unweighted("MultiKrum", models, weights)
         models[0]  # IndexError for an empty list, as FedAvg
         m = len(models) - cls.f if cls.m is None else cls.m
-        return krum_modules(models, cls.f, m, to_host=to_host)
+        return krum_modules(models, cls.f, m, to_host=to_host, distance=cls.distance)
 
     @classmethod
-    def with_params(cls, f: int, m: Optional[int] = None):
+    def with_params(cls, f: int, m: Optional[int] = None, distance: str = "exact"):
         """A MultiKrum class for Byzantine count f that averages m models
-        (None: n - f of the n it is given)."""
+        (None: n - f of the n it is given). distance: "exact" or "gram"."""
         f = int(f)
         if f < 0:
             raise ValueError(f"f must be >= 0 (got {f})")
@@ -233,7 +243,8 @@ class MultiKrum(GradientAggregation):
             m = int(m)
             if m < 1:
                 raise ValueError(f"m must be >= 1 (got {m})")
-        return type(f"MultiKrum{f}" + ("" if m is None else f"x{m}"), (cls,), {"f": f, "m": m})
+        return type(f"MultiKrum{f}" + ("" if m is None else f"x{m}"), (cls,),
+                    {"f": f, "m": m, "distance": check_distance_method(distance)})
 
 
 class Bulyan(GradientAggregation):
@@ -254,18 +265,19 @@ class Bulyan(GradientAggregation):
     task by task (no batched form yet)."""
 
     f = 1
+    distance = "exact"
 
     @classmethod
     def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
                   to_host: Optional[bool] = None) -> nn.Module:
         _check_unweighted("Bulyan", models, weights)
-        return bulyan_modules(models, cls.f, to_host=to_host)
+        return bulyan_modules(models, cls.f, to_host=to_host, distance=cls.distance)
 
     @classmethod
-    def with_params(cls, f: int):
+    def with_params(cls, f: int, distance: str = "exact"):
         """A Bulyan class for Byzantine count f: the plugin signature
-        ModelManager calls."""
+        ModelManager calls. distance: "exact" or "gram"."""
         f = int(f)
         if f < 0:
             raise ValueError(f"f must be >= 0 (got {f})")
-        return type(f"Bulyan{f}", (cls,), {"f": f})
+        return type(f"Bulyan{f}", (cls,), {"f": f, "distance": check_distance_method(distance)})

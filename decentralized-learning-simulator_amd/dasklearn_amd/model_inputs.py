@@ -210,7 +210,8 @@ def nearest_modules(models: List[nn.Module], keep_fn, device=None, to_host: Opti
     return inputs.module(outs, to_host)
 
 
-def bulyan_modules(models: List[nn.Module], f: int, to_host: Optional[bool] = None) -> nn.Module:
+def bulyan_modules(models: List[nn.Module], f: int, to_host: Optional[bool] = None,
+                   distance: str = "exact") -> nn.Module:
     """Bulyan of `models` with Byzantine count f (gradient_aggregation/krum.py
     has the rule): the distance matrix on the GPU (model_distances), the
     selection of theta = n - 2f models on the host (krum.bulyan_select), then
@@ -221,14 +222,15 @@ def bulyan_modules(models: List[nn.Module], f: int, to_host: Optional[bool] = No
     Buffers, attributes and parameter strides are copy.deepcopy(models[0])'s,
     also when models[0] is not selected; the result lives where models[0] lives
     unless to_host says otherwise. One D2H copy of n*n doubles and one stream
-    synchronisation per call, as krum_modules."""
+    synchronisation per call, as krum_modules. distance: model_distances' method."""
     from dasklearn_amd.gradient_aggregation import krum as _krum
     models[0]  # IndexError for an empty list, as FedAvg
     n = len(models)
     _native.check_pairdist_fan_in(n)
     _krum.check_bulyan_params(n, f)
+    check_distance_method(distance)
     inputs = ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance")
-    chosen = _krum.bulyan_select(_distances(inputs).tolist(), f)  # waits for the stream: the staged sources may go
+    chosen = _krum.bulyan_select(_distances(inputs, distance).tolist(), f)  # waits for the stream: the staged sources may go
     outs = _nearest_outs(inputs, chosen, len(chosen) - 2 * f, inputs.host_out(to_host))
     return inputs.module(outs, to_host)
 
@@ -276,19 +278,32 @@ def robust_arena_tasks(prepared: List[ArenaTask], lo_hi_fn, on_launched=None) ->
     return finish_modules(prepared, outs, on_launched)
 
 
-def _distances(inputs: ModelInputs) -> torch.Tensor:
+DISTANCE_METHODS = ("exact", "gram")
+
+
+def check_distance_method(method: str) -> str:
+    """ValueError unless `method` is one of DISTANCE_METHODS."""
+    if method not in DISTANCE_METHODS:
+        raise ValueError(f"the distance method must be one of {', '.join(repr(m) for m in DISTANCE_METHODS)} "
+                         f"(got {method!r})")
+    return method
+
+
+def _distances(inputs: ModelInputs, method: str = "exact") -> torch.Tensor:
     n, dev, layout = inputs.n, inputs.dev, inputs.layout
     with torch.no_grad(), torch.cuda.device(dev):
         raw_stream = torch._C._cuda_getCurrentRawStream(dev.index)
         d2 = torch.empty(n * n, dtype=torch.float64, device=dev)
         first = True
         for dt, kind, data in inputs:
+            # the Gram kernel takes no fp64 (its products would not be exact): such a group stays exact
+            gram = method == "gram" and dt != torch.float64
             if kind == "flat":
-                _native.pairwise_sqdist(data, d2, accumulate=not first)
+                (_native.gram_sqdist if gram else _native.pairwise_sqdist)(data, d2, accumulate=not first)
             else:
-                _native.pairwise_sqdist_tensors_raw([p for ptrs in data for p in ptrs], n, layout.split_sizes[dt],
-                                                    _native.dtype_code(dt, single_task=True), d2.data_ptr(),
-                                                    not first, raw_stream)
+                tensors_raw = _native.gram_sqdist_tensors_raw if gram else _native.pairwise_sqdist_tensors_raw
+                tensors_raw([p for ptrs in data for p in ptrs], n, layout.split_sizes[dt],
+                            _native.dtype_code(dt, single_task=True), d2.data_ptr(), not first, raw_stream)
             first = False
         if first:
             d2.zero_()
@@ -296,7 +311,7 @@ def _distances(inputs: ModelInputs) -> torch.Tensor:
     return host.reshape(n, n)
 
 
-def model_distances(models: List[nn.Module], device=None) -> torch.Tensor:
+def model_distances(models: List[nn.Module], device=None, method: str = "exact") -> torch.Tensor:
     """The [n, n] float64 host matrix of squared L2 distances between the
     models' parameters (dlsim_pairwise_sqdist): entry [i][j] is the sum over
     every parameter element of (double(x_i) - double(x_j))^2, bitwise
@@ -304,8 +319,20 @@ def model_distances(models: List[nn.Module], device=None) -> torch.Tensor:
     dtype groups of models[0]'s layout add into the one matrix in layout
     order. A model whose parameter list differs from models[0]'s raises
     ValueError; more than 32 models too; an empty list IndexError. The matrix
-    comes back with one D2H copy of n*n doubles, which waits for the stream."""
-    return _distances(ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance", device))
+    comes back with one D2H copy of n*n doubles, which waits for the stream.
+
+    method "gram" sends every fp32, bf16 and fp16 dtype group through
+    dlsim_gram_sqdist instead (the Gram matrix of the rows centred on
+    models[0], on the fp64 matrix unit: every row read once at any n; measured
+    faster than the exact kernel for fp32 from n = 16 on, slower at n <= 8 and
+    for bf16 at n = 16): an entry is then within 2 (P + 16) 2^-53
+    (S_i + S_j) of the exact one per group, S_i the squared distance of model i
+    to models[0], and NaN when model i or j holds a NaN or infinite parameter
+    (where the exact entry tells NaN from +Inf). An fp64 group goes through the
+    exact kernel under either method, accumulating into the same matrix. Any
+    other string raises ValueError."""
+    check_distance_method(method)
+    return _distances(ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance", device), method)
 
 
 def distances_arena_tasks(prepared: List[ArenaTask]) -> List[torch.Tensor]:
@@ -704,7 +731,8 @@ def _copy_of_params(model0: nn.Module, layout: ParamLayout, params, views, dev: 
     return _restride(module_from_arenas(model0, layout, arenas), layout)
 
 
-def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Optional[bool] = None) -> nn.Module:
+def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Optional[bool] = None,
+                 distance: str = "exact") -> nn.Module:
     """Krum (m None) or Multi-Krum(m) of `models` with Byzantine count f
     (gradient_aggregation/krum.py has the rule): the distance matrix on the
     GPU (model_distances), the selection on the host, then Krum copies the
@@ -716,14 +744,15 @@ def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Opt
     to_host says otherwise.
 
     The selection needs the matrix on the host: one D2H copy of n*n doubles
-    and one stream synchronisation per call."""
+    and one stream synchronisation per call. distance: model_distances' method."""
     from dasklearn_amd.gradient_aggregation import krum as _krum
     model0 = models[0]  # IndexError for an empty list, as FedAvg
     n = len(models)
     _native.check_pairdist_fan_in(n)
     _krum.check_krum_params(n, f, 1 if m is None else m)
+    check_distance_method(distance)
     inputs = ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance")
-    chosen = _krum.krum_select(_distances(inputs).tolist(), f, 1 if m is None else m)
+    chosen = _krum.krum_select(_distances(inputs, distance).tolist(), f, 1 if m is None else m)
     host_out = inputs.host_out(to_host)
     if m is None:
         w = chosen[0]

@@ -20,7 +20,9 @@ the median, MeanAroundMedian, which keeps the n - 2*`aggregation_trim` values
 closest to the median; MULTI_KRUM with `settings.aggregation_krum_rule =
 "bulyan"` (default "multi_krum") is Bulyan with Byzantine count
 `aggregation_byzantine` (`aggregation_multi_krum_m` must then be None). Any
-other string raises ValueError. The
+other string raises ValueError. KRUM and MULTI_KRUM (both of its rules) take
+their distance matrix from the kernel `settings.aggregation_distance` names:
+"exact" (the default) or "gram" (krum.py; any other string raises ValueError). The
 `dataset` argument is accepted and ignored, as the reference's aggregate task
 passes None (functions.py:99).
 """
@@ -54,6 +56,11 @@ def krum_rule_name(settings) -> str:
     return _rule(settings, "aggregation_krum_rule", ("multi_krum", "bulyan"))
 
 
+def distance_name(settings) -> str:
+    """"exact" (the default) or "gram": the distance kernel of KRUM and MULTI_KRUM."""
+    return _rule(settings, "aggregation_distance", ("exact", "gram"))
+
+
 class ModelManager:
 
     def __init__(self, dataset, settings, participant_index: int):
@@ -82,7 +89,8 @@ class ModelManager:
                 return MeanAroundMedian.with_trim(trim)
             return TrimmedMean.with_trim(trim)
         if method == GradientAggregationMethod.KRUM:
-            return Krum.with_params(getattr(self.settings, "aggregation_byzantine", 1))
+            return Krum.with_params(getattr(self.settings, "aggregation_byzantine", 1),
+                                    distance=distance_name(self.settings))
         if method == GradientAggregationMethod.MULTI_KRUM:
             f = getattr(self.settings, "aggregation_byzantine", 1)
             m = getattr(self.settings, "aggregation_multi_krum_m", None)
@@ -90,8 +98,8 @@ class ModelManager:
                 if m is not None:
                     raise ValueError(f"aggregation_krum_rule = 'bulyan' selects n - 2f models itself: "
                                      f"aggregation_multi_krum_m must be None (got {m})")
-                return Bulyan.with_params(f)
-            return MultiKrum.with_params(f, m)
+                return Bulyan.with_params(f, distance=distance_name(self.settings))
+            return MultiKrum.with_params(f, m, distance=distance_name(self.settings))
         if method == GradientAggregationMethod.GEOMETRIC_MEDIAN:
             return GeometricMedian.with_params(getattr(self.settings, "aggregation_gm_iters", 3),
                                                getattr(self.settings, "aggregation_gm_nu", 1e-6))

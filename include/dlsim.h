@@ -848,6 +848,64 @@ int dlsim_pairwise_sqdist_tensors(const void* const* d_inputs, int n, int t, con
 int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
 
 /*
+ * dlsim_gram_sqdist: the matrix of dlsim_pairwise_sqdist through the Gram
+ * matrix of the centred rows on the fp64 matrix unit (v_mfma_f64_16x16x4_f64;
+ * DESIGN.md 8u). An opt-in second entry with a contract of its own: it reads
+ * every row once at any n, where dlsim_pairwise_sqdist reads a row once per
+ * 8-row unit it belongs to (5.5 times at n = 32), and is not bit-identical to
+ * it. (New: no reference counterpart.)
+ *   s(v)      = v if v is finite, otherwise 0
+ *   c[e]      = s(x_0[e])
+ *   y_i[e]    = double(s(x_i[e])) - double(c[e])      (one double subtraction; y_0 = 0)
+ *   G_ij      = sum over e of y_i[e] * y_j[e]         (accumulated in double by the matrix unit)
+ *   d_d2[i*n + j] = max(+0.0, G_ii + G_jj - 2 * G_ij) for i < j, computed once
+ *               and stored to both halves (the same bits); d_d2[i*n + i] = +0.0
+ * If row i or row j holds a NaN or an infinite element, d_d2[i*n + j] is NaN
+ * (a coarser class than the exact entry's NaN / +Inf; Krum maps both to +Inf).
+ * Entries between finite rows are unaffected by other rows, row 0 included:
+ * the identity holds for any centre.
+ * Accuracy: with S_i = sum_e (x_i[e] - c[e])^2, a finite entry is within
+ *   2 * (n_elems + 16) * 2^-53 * (S_i + S_j)
+ * absolute of the exact sum_e (x_i[e] - x_j[e])^2: the error is relative to
+ * the rows' distances to row 0, not to their norms.
+ *   n       1 <= n <= DLSIM_MAX_GRAMDIST_INPUTS
+ *   dtype   DLSIM_F32, DLSIM_BF16 or DLSIM_F16. DLSIM_F64 is DLSIM_E_DTYPE:
+ *           products of fp64 values are not exact in double and their squares
+ *           can overflow; fp64 models take dlsim_pairwise_sqdist.
+ * d_inputs, d_d2, accumulate, n == 1, n_elems == 0, alignment, aliasing and
+ * the argument errors (decided before any HIP call) are those of
+ * dlsim_pairwise_sqdist. No atomics: per-block partial Gram blocks and row
+ * masks go to a stream-ordered workspace and a second kernel adds them in
+ * block order; grid and tile are a function of (n, dtype, n_elems, whether
+ * every input is 16-byte aligned) only, so two calls with the same arguments
+ * return the same bits. Stream-ordered.
+ */
+#define DLSIM_MAX_GRAMDIST_INPUTS 32
+int dlsim_gram_sqdist(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,
+                      void* stream);
+
+/*
+ * dlsim_gram_sqdist_tensors: dlsim_gram_sqdist over t separate tensors per
+ * model, summed into one matrix; arguments as dlsim_pairwise_sqdist_tensors.
+ * Bit-identical to t dlsim_gram_sqdist calls in order, the first with the
+ * caller's `accumulate` and the rest with 1: each tensor is centred and
+ * clamped on its own, and a row with a non-finite element in any tensor gives
+ * NaN entries. Errors are decided for the whole list before the first launch.
+ * (New: no reference counterpart.)
+ */
+int dlsim_gram_sqdist_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems, int dtype,
+                              double* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_gramdist_geometry: the tile (elements a block takes per step) and the
+ * grid dlsim_gram_sqdist uses for n 16-byte-aligned inputs of n_elems elements
+ * of dtype, dealt as dlsim_pairdist_geometry describes. Misaligned inputs
+ * take tiles of 128 elements under the same rule. Host only. (New: no
+ * reference counterpart.)
+ */
+int dlsim_gramdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
+
+/*
  * dlsim_pairwise_sqdist_batched: b independent dlsim_pairwise_sqdist_tensors
  * tasks in a few launches (the Krum or Multi-Krum distance matrices, or the
  * consensus distances, of one simulated round's peers). The

@@ -33,7 +33,16 @@ rows (for DESIGN.md §8k).
            in one batched call against two calls of the flat entry: large
            tasks inside the batched kernel.
 
+  gram     (--gram, instead of the above) dlsim_gram_sqdist
+           beside dlsim_pairwise_sqdist and the yardstick on the same rows in
+           the same process (legs yard_1, pairdist, gram, yard_2; the same
+           windows, rotation and decoy rule): fp32 at 11,181,642 elements with
+           n = 4, 8, 16, 32, bf16 at 125,000,000 with n = 8 and 16; then one
+           Krum and one Bulyan aggregate of 17 and of 32 ResNet-18-shaped
+           device-arena models with distance "exact" and "gram".
+
     python scripts/bench_krum.py [--windows 5] [--launches 200] [--skip-bf16] [--out FILE]
+    python scripts/bench_krum.py --gram [--windows 5] [--launches 200] [--skip-bf16] [--out FILE]
     python scripts/bench_krum.py --batch [--windows 7] [--launches N] [--legs abcd] [--out FILE]
 One JSON line per measurement (also written to --out). --launches is the number
 of whole calls per window of legs (a), (c) and (d): 20 in (a), where a call is
@@ -59,7 +68,7 @@ from torch import nn  # noqa: E402
 from dasklearn_amd import _native, arena  # noqa: E402
 from dasklearn_amd.arena import aligned_empty, arena_empty, base_align, row_stride  # noqa: E402
 from dasklearn_amd.gradient_aggregation.fedavg import FedAvg  # noqa: E402
-from dasklearn_amd.gradient_aggregation.krum import Krum, MultiKrum  # noqa: E402
+from dasklearn_amd.gradient_aggregation.krum import Bulyan, Krum, MultiKrum  # noqa: E402
 
 LINES = []
 
@@ -70,20 +79,20 @@ def emit(line):
 
 
 class DistPlan:
-    """One prepared dlsim_pairwise_sqdist call (pointers resolved once, as ReducePlan)."""
+    """One prepared dlsim_pairwise_sqdist (or `entry`) call (pointers resolved once, as ReducePlan)."""
 
-    def __init__(self, inputs, d2):
+    def __init__(self, inputs, d2, entry="dlsim_pairwise_sqdist"):
         n = len(inputs)
         self._keep = (list(inputs), d2)
         self.args = ((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, inputs[0].numel(),
                      _native.dtype_code(inputs[0].dtype, single_task=True), ctypes.c_void_p(d2.data_ptr()), 0)
-        self.lib = _native.load()
+        self.entry, self.fn = entry, getattr(_native.load(), entry)
         self.device = d2.device
 
     def launch(self, stream=None):
-        rc = self.lib.dlsim_pairwise_sqdist(*self.args, _native._stream_handle(self.device, stream))
+        rc = self.fn(*self.args, _native._stream_handle(self.device, stream))
         if rc:
-            _native._check("dlsim_pairwise_sqdist", rc)
+            _native._check(self.entry, rc)
 
 
 def windows(plans, launches, nwin):
@@ -105,7 +114,7 @@ def windows(plans, launches, nwin):
     return sorted(out)
 
 
-def kernel_lines(P, tdt, n, launches, nwin):
+def kernel_lines(P, tdt, n, launches, nwin, gram=False):
     dev = torch.device("cuda", 0)
     esz = torch.empty((), dtype=tdt).element_size()
     byts = n * P * esz
@@ -130,9 +139,10 @@ def kernel_lines(P, tdt, n, launches, nwin):
     base = {"params": P, "dtype": str(tdt).replace("torch.", ""), "n": n, "bytes": byts, "rotating_sets": sets,
             "launches_per_window": launches, "windows": nwin}
     res = {}
-    for key in ("yard_1", "pairdist", "yard_2"):
-        if key == "pairdist":
-            plans = [DistPlan(ins[j], d2s[j]) for j in range(sets)]
+    for key in ("yard_1", "pairdist", "gram", "yard_2") if gram else ("yard_1", "pairdist", "yard_2"):
+        if key in ("pairdist", "gram"):
+            entry = "dlsim_gram_sqdist" if key == "gram" else "dlsim_pairwise_sqdist"
+            plans = [DistPlan(ins[j], d2s[j], entry) for j in range(sets)]
             moved = byts
         else:
             plans = [_native.ReducePlan(ins[j % sets], w, outs[j], _native.DLSIM_EXACT) for j in range(out_sets)]
@@ -142,16 +152,22 @@ def kernel_lines(P, tdt, n, launches, nwin):
         line = dict(base, leg=key, median_us=round(ws[len(ws) // 2], 3), min_us=round(ws[0], 3),
                     max_us=round(ws[-1], 3), algorithmic_bytes=moved, GBps=round(moved / ws[len(ws) // 2] / 1e3, 1),
                     kernel="dlsim::k_pairdist + dlsim::k_pairdist_finish" if key == "pairdist"
+                    else "dlsim::k_gramdist + dlsim::k_gramdist_finish" if key == "gram"
                     else _native.kernel_name(n, P, tdt))
         if key == "pairdist":
             line.update(tile_elems=tile, blocks=blocks)
+        if key == "gram":
+            gt, gb = _native.gramdist_geometry(n, tdt, P)
+            line.update(tile_elems=gt, blocks=gb)
         emit(line)
     yard_us = (res["yard_1"] + res["yard_2"]) / 2
+    extra = {"gram_over_yard": round(res["gram"] / yard_us, 4),
+             "gram_over_pairdist": round(res["gram"] / res["pairdist"], 4)} if gram else {}
     emit(dict(base, leg="ratio", pairdist_over_yard=round(res["pairdist"] / yard_us, 4),
-              yard_spread=round(abs(res["yard_1"] - res["yard_2"]) / yard_us, 4)))
+              yard_spread=round(abs(res["yard_1"] - res["yard_2"]) / yard_us, 4), **extra))
 
 
-def plugin_lines(reps=20):
+def plugin_lines(reps=20, gram=False):
     sys.path.insert(0, ROOT)
     from bench import resnet18_shapes
     dev = torch.device("cuda", 0)
@@ -163,10 +179,22 @@ def plugin_lines(reps=20):
             g = torch.Generator().manual_seed(seed)
             self.ps = nn.ParameterList([nn.Parameter(torch.randn(sh, generator=g) * 0.05) for sh in shapes])
 
-    n = 8
-    models = [arena.to_device_arena(Shaped(100 + i), dev) for i in range(n)]
-    for name, agg in (("FedAvg", FedAvg), ("Krum(f=2)", Krum.with_params(2)), ("MultiKrum(f=2)", MultiKrum.with_params(2)),
-                      ("FedAvg_again", FedAvg)):
+    cases = [(8, (("FedAvg", FedAvg), ("Krum(f=2)", Krum.with_params(2)), ("MultiKrum(f=2)", MultiKrum.with_params(2)),
+                  ("FedAvg_again", FedAvg)))]
+    if gram:  # the distance kernels inside one aggregate: exact, gram, exact again
+        cases = [(n, tuple((f"{cls.__name__}(f={f}, {d})", cls.with_params(f, distance=d))
+                           for cls in (Krum, Bulyan) for d in ("exact", "gram", "exact")))
+                 for n, f in ((17, 3), (32, 7))]
+    for n, aggs in cases:
+        models = [arena.to_device_arena(Shaped(100 + i), dev) for i in range(n)]
+        plugin_case_lines(models, aggs, reps, shapes)
+        del models
+        torch.cuda.empty_cache()
+
+
+def plugin_case_lines(models, aggs, reps, shapes):
+    n = len(models)
+    for name, agg in aggs:
         ts = []
         for k in range(reps + 3):
             torch.cuda.synchronize()
@@ -363,6 +391,7 @@ def main():
     ap.add_argument("--skip-bf16", action="store_true")
     ap.add_argument("--batch", action="store_true", help="the batched entry's legs (a)-(d) instead of the flat kernel's")
     ap.add_argument("--legs", default="abcd", help="with --batch: which of the legs a, b, c, d")
+    ap.add_argument("--gram", action="store_true", help="dlsim_gram_sqdist beside the exact kernel and the yardstick")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -377,12 +406,12 @@ def main():
         return
     a.launches = a.launches or 200
     for n in (4, 8, 16, 32):
-        kernel_lines(11_181_642, torch.float32, n, a.launches, a.windows)
+        kernel_lines(11_181_642, torch.float32, n, a.launches, a.windows, a.gram)
         torch.cuda.empty_cache()
-    if not a.skip_bf16:
-        kernel_lines(125_000_000, torch.bfloat16, 8, a.launches, a.windows)
+    for n in () if a.skip_bf16 else (8, 16) if a.gram else (8,):
+        kernel_lines(125_000_000, torch.bfloat16, n, a.launches, a.windows, a.gram)
         torch.cuda.empty_cache()
-    plugin_lines()
+    plugin_lines(gram=a.gram)
     write_out(a.out)
 
 
