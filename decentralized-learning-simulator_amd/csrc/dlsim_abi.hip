@@ -324,6 +324,10 @@ void pairdist_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsig
 hipError_t gramdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
                          hipStream_t st);
 void gramdist_geometry(int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
+// its wide form, n <= 128 (inst_gramwide.hip)
+hipError_t gramwide_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
+                         hipStream_t st);
+void gramwide_geometry(int n, int dtype, size_t nelem, size_t* tile_elems, unsigned* blocks);
 hipError_t pairdist_batched(int b, const int* fan_in, const int* n_tensors, const void* const* in,
                             const size_t* nelem, int dtype, double* const* d2s, int accumulate, hipStream_t st);
 hipError_t reducedist_flat(const void* const* in, int n, const double* w, void* out, size_t nelem, int dtype,
@@ -366,6 +370,7 @@ void mx_batch_limits(int* max_tasks, int* max_slots);
 constexpr const char* kRobustLimit = "the sorting network is held in registers";
 constexpr const char* kPairdistLimit = "the pairs' accumulators are held in registers";
 constexpr const char* kGramdistLimit = "two row blocks of the 16 x 16 matrix instruction";
+constexpr const char* kGramwideLimit = "eight row blocks of the 16 x 16 matrix instruction";
 constexpr const char* kReducedistLimit = "the inputs' rows and accumulators are held in registers";
 constexpr const char* kSparseLimit = "the 32-row bound of the robust, distance and reduce-and-measure entries";
 
@@ -1447,11 +1452,12 @@ int dlsim_pairdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems
 }
 
 // dtype first and without fp64 (DLSIM_E_DTYPE), then n and accumulate: the checks the Gram entries share
-static int check_gram(int n, int dtype, int accumulate) {
+static int check_gram(int n, int dtype, int accumulate, int max = DLSIM_MAX_GRAMDIST_INPUTS,
+                      const char* why = kGramdistLimit) {
   if (dtype == DLSIM_F64)
     return fail(DLSIM_E_DTYPE, "the Gram distance takes DLSIM_F32, DLSIM_BF16 and DLSIM_F16: products of fp64 values "
                                "are not exact in double (use dlsim_pairwise_sqdist)");
-  int rc = check_fan_in(n, DLSIM_MAX_GRAMDIST_INPUTS, dtype, kGramdistLimit);
+  int rc = check_fan_in(n, max, dtype, why);
   if (rc == DLSIM_OK) rc = check_accumulate(accumulate);
   return rc;
 }
@@ -1504,6 +1510,57 @@ int dlsim_gramdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems
   if (rc != DLSIM_OK) return rc;
   if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
   gramdist_geometry(dtype, n_elems, tile_elems, blocks);
+  return DLSIM_OK;
+}
+
+int dlsim_gram_sqdist_wide(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,
+                           void* stream) {
+  g_err.clear();
+  int rc = check_gram(n, dtype, accumulate, DLSIM_MAX_GRAMWIDE_INPUTS, kGramwideLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
+  if (!d_d2) return fail(DLSIM_E_ARG, "null distance matrix pointer");
+  rc = check_inputs_apart(d_inputs, 1, n, n_elems * elem_bytes(dtype), addr(d_d2),
+                          addr(d_d2) + sizeof(double) * static_cast<size_t>(n) * n, "the distance matrix");
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = gramwide_flat(d_inputs, n, n_elems, dtype, d_d2, accumulate, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "wide Gram distance launch");
+}
+
+int dlsim_gram_sqdist_wide_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems, int dtype,
+                                   double* d_d2, int accumulate, void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_gram(n, dtype, accumulate, DLSIM_MAX_GRAMWIDE_INPUTS, kGramwideLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_d2) return fail(DLSIM_E_ARG, "null distance matrix pointer");
+  if (t > 0 && (!d_inputs || !n_elems)) return fail(DLSIM_E_ARG, "null array argument");
+  const size_t ts = static_cast<size_t>(t);
+  for (int k = 0; k < t; ++k) {
+    rc = check_inputs_apart(d_inputs + k, ts, n, n_elems[k] * elem_bytes(dtype), addr(d_d2),
+                            addr(d_d2) + sizeof(double) * static_cast<size_t>(n) * n, "the distance matrix");
+    if (rc != DLSIM_OK) return fail(rc, "tensor %d: %s", k, std::string(g_err).c_str());
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (t == 0) {
+    const hipError_t e = gramwide_flat(nullptr, n, 0, dtype, d_d2, accumulate, st);
+    return e == hipSuccess ? DLSIM_OK : hip_fail(e, "wide Gram distance launch");
+  }
+  const void* row[DLSIM_MAX_GRAMWIDE_INPUTS];
+  for (int k = 0; k < t; ++k) {
+    gather_row(d_inputs, n, t, k, row);
+    const hipError_t e = gramwide_flat(row, n, n_elems[k], dtype, d_d2, k == 0 ? accumulate : 1, st);
+    if (e != hipSuccess) return hip_fail(e, "wide Gram distance launch");
+  }
+  return DLSIM_OK;
+}
+
+int dlsim_gramwide_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks) {
+  g_err.clear();
+  const int rc = check_gram(n, dtype, 0, DLSIM_MAX_GRAMWIDE_INPUTS, kGramwideLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!tile_elems || !blocks) return fail(DLSIM_E_ARG, "null result pointer");
+  gramwide_geometry(n, dtype, n_elems, tile_elems, blocks);
   return DLSIM_OK;
 }
 

@@ -75,6 +75,9 @@ EXPORTS = (
     "dlsim_gram_sqdist",
     "dlsim_gram_sqdist_tensors",
     "dlsim_gramdist_geometry",
+    "dlsim_gram_sqdist_wide",
+    "dlsim_gram_sqdist_wide_tensors",
+    "dlsim_gramwide_geometry",
     "dlsim_pairwise_sqdist_batched",
     "dlsim_pairdist_batch_geometry",
     "dlsim_wreduce_dist_batched",
@@ -289,6 +292,12 @@ def load() -> ctypes.CDLL:
         lib.dlsim_gram_sqdist_tensors.restype = i
         lib.dlsim_gramdist_geometry.argtypes = lib.dlsim_pairdist_geometry.argtypes
         lib.dlsim_gramdist_geometry.restype = i
+        lib.dlsim_gram_sqdist_wide.argtypes = lib.dlsim_pairwise_sqdist.argtypes
+        lib.dlsim_gram_sqdist_wide.restype = i
+        lib.dlsim_gram_sqdist_wide_tensors.argtypes = lib.dlsim_pairwise_sqdist_tensors.argtypes
+        lib.dlsim_gram_sqdist_wide_tensors.restype = i
+        lib.dlsim_gramwide_geometry.argtypes = lib.dlsim_pairdist_geometry.argtypes
+        lib.dlsim_gramwide_geometry.restype = i
         lib.dlsim_pairwise_sqdist_batched.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i), ctypes.POINTER(vp),
                                                       ctypes.POINTER(sz), i, ctypes.POINTER(vp), i, vp]
         lib.dlsim_pairwise_sqdist_batched.restype = i
@@ -620,6 +629,7 @@ SGD_MOMENTUM_TENSORS_PER_LAUNCH = 64  # csrc/sgdm_kernels.hpp kSgdmMaxTensors
 MAX_ROBUST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_ROBUST_INPUTS
 MAX_PAIRDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_PAIRDIST_INPUTS
 MAX_REDUCEDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_REDUCEDIST_INPUTS
+MAX_GRAMWIDE_INPUTS = 128  # include/dlsim.h DLSIM_MAX_GRAMWIDE_INPUTS
 
 
 def _check_fan_in(n: int, limit: int, message: str) -> None:
@@ -635,6 +645,10 @@ def check_robust_fan_in(n: int) -> None:
 
 def check_pairdist_fan_in(n: int) -> None:
     _check_fan_in(n, MAX_PAIRDIST_INPUTS, "the pairwise-distance kernels take at most {limit} models (got {n})")
+
+
+def check_gramwide_fan_in(n: int) -> None:
+    _check_fan_in(n, MAX_GRAMWIDE_INPUTS, "the wide Gram distance kernels take at most {limit} models (got {n})")
 
 
 def check_reducedist_fan_in(n: int) -> None:
@@ -1267,6 +1281,37 @@ def gramdist_geometry(n: int, torch_dtype, numel: int):
     """(tile elements, blocks) of dlsim_gram_sqdist for n 16-byte-aligned
     inputs of numel elements (dlsim_gramdist_geometry; no GPU needed)."""
     return _geometry("dlsim_gramdist_geometry", n, torch_dtype, numel)
+
+
+def gram_sqdist_wide(inputs, out, accumulate: bool = False, stream=None):
+    """dlsim_gram_sqdist_wide: gram_sqdist for up to 128 inputs, the same
+    contract and bound; n <= 32 gives gram_sqdist's bits."""
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_gramwide_fan_in(n)
+    _check_distances(out, n * n, "matrix")
+    dt, numel = _check_flat_inputs(inputs, None, out.device, "Gram distance")
+    _check("dlsim_gram_sqdist_wide",
+           load().dlsim_gram_sqdist_wide(_ptr_array([t.data_ptr() for t in inputs]), n, numel,
+                                         dtype_code(dt, single_task=True), out.data_ptr(), int(bool(accumulate)),
+                                         _stream_handle(out.device, stream)))
+    return out
+
+
+def gram_sqdist_wide_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], dtype: int, out_ptr: int,
+                                 accumulate: bool, stream_handle) -> None:
+    """dlsim_gram_sqdist_wide_tensors, as pairwise_sqdist_tensors_raw."""
+    check_gramwide_fan_in(n)
+    _check("dlsim_gram_sqdist_wide_tensors",
+           load().dlsim_gram_sqdist_wide_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels), dtype,
+                                                 out_ptr, int(bool(accumulate)), stream_handle))
+
+
+def gramwide_geometry(n: int, torch_dtype, numel: int):
+    """(tile elements, blocks) of dlsim_gram_sqdist_wide for n inputs of numel
+    elements (dlsim_gramwide_geometry; no GPU needed)."""
+    return _geometry("dlsim_gramwide_geometry", n, torch_dtype, numel)
 
 
 def pairwise_sqdist_batched_raw(fan_in: Sequence[int], n_tensors: Sequence[int], in_ptrs: Sequence[int],

@@ -46,8 +46,13 @@ on its own. A device-side selection is not implemented.
 take the matrix from the Gram kernel instead (csrc/gramdist_kernels.hpp,
 DESIGN.md §8u): every model read once at any n, an error bound relative to the
 models' distances to models[0], NaN for both non-finite classes (which the rule
-above maps to +Inf alike). Such a plugin's aggregates of a round run task by
-task. The default everywhere is "exact".
+above maps to +Inf alike). `distance="wide"` is the same contract for up to
+128 models (csrc/gramwide_kernels.hpp; the same bits as "gram"
+up to 32): Krum and Multi-Krum over a server round's 50 to 100 sampled
+clients, and Bulyan while its second stage's n - 2f models stay within 32.
+Past 32 models fp64 parameters raise ValueError. Such plugins' aggregates of a
+round run task by task. The default everywhere is "exact", with its limit of
+32 models.
 """
 import math
 from typing import List, Optional, Sequence
@@ -208,7 +213,7 @@ class Krum(GradientAggregation):
     def with_params(cls, f: int, m: Optional[int] = None, distance: str = "exact"):
         """A Krum class for Byzantine count f: the plugin signature
         ModelManager calls. m is accepted for symmetry and must be None or 1.
-        distance: "exact" or "gram" (model_distances' method)."""
+        distance: "exact", "gram" or "wide" (model_distances' method)."""
         f = int(f)
         if f < 0:
             raise ValueError(f"f must be >= 0 (got {f})")
@@ -235,7 +240,7 @@ class MultiKrum(GradientAggregation):
     @classmethod
     def with_params(cls, f: int, m: Optional[int] = None, distance: str = "exact"):
         """A MultiKrum class for Byzantine count f that averages m models
-        (None: n - f of the n it is given). distance: "exact" or "gram"."""
+        (None: n - f of the n it is given). distance: "exact", "gram" or "wide"."""
         f = int(f)
         if f < 0:
             raise ValueError(f"f must be >= 0 (got {f})")
@@ -276,7 +281,7 @@ class Bulyan(GradientAggregation):
     @classmethod
     def with_params(cls, f: int, distance: str = "exact"):
         """A Bulyan class for Byzantine count f: the plugin signature
-        ModelManager calls. distance: "exact" or "gram"."""
+        ModelManager calls. distance: "exact", "gram" or "wide"."""
         f = int(f)
         if f < 0:
             raise ValueError(f"f must be >= 0 (got {f})")

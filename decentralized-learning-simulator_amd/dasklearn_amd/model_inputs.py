@@ -222,14 +222,20 @@ def bulyan_modules(models: List[nn.Module], f: int, to_host: Optional[bool] = No
     Buffers, attributes and parameter strides are copy.deepcopy(models[0])'s,
     also when models[0] is not selected; the result lives where models[0] lives
     unless to_host says otherwise. One D2H copy of n*n doubles and one stream
-    synchronisation per call, as krum_modules. distance: model_distances' method."""
+    synchronisation per call, as krum_modules. distance: model_distances' method;
+    under "wide" up to 128 models while n - 2f <= 32, the second stage's
+    capacity (ValueError otherwise, before any device work)."""
     from dasklearn_amd.gradient_aggregation import krum as _krum
     models[0]  # IndexError for an empty list, as FedAvg
     n = len(models)
-    _native.check_pairdist_fan_in(n)
+    _check_distance_fan_in(n, distance)
     _krum.check_bulyan_params(n, f)
     check_distance_method(distance)
-    inputs = ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance")
+    if n - 2 * f > _native.MAX_ROBUST_INPUTS:
+        raise ValueError(f"Bulyan over n = {n} models with f = {f}: the second stage reads the n - 2f = {n - 2 * f} "
+                         f"selected models, and the mean-around-the-median kernel takes at most "
+                         f"{_native.MAX_ROBUST_INPUTS}")
+    inputs = _distance_inputs(models, distance)
     chosen = _krum.bulyan_select(_distances(inputs, distance).tolist(), f)  # waits for the stream: the staged sources may go
     outs = _nearest_outs(inputs, chosen, len(chosen) - 2 * f, inputs.host_out(to_host))
     return inputs.module(outs, to_host)
@@ -278,7 +284,7 @@ def robust_arena_tasks(prepared: List[ArenaTask], lo_hi_fn, on_launched=None) ->
     return finish_modules(prepared, outs, on_launched)
 
 
-DISTANCE_METHODS = ("exact", "gram")
+DISTANCE_METHODS = ("exact", "gram", "wide")
 
 
 def check_distance_method(method: str) -> str:
@@ -289,21 +295,46 @@ def check_distance_method(method: str) -> str:
     return method
 
 
+def _check_distance_fan_in(n: int, method: str) -> None:
+    """ValueError past the model count that `method`'s kernels take: 128 under "wide", else 32."""
+    if method == "wide":
+        _native.check_gramwide_fan_in(n)
+    else:
+        _native.check_pairdist_fan_in(n)
+
+
+def _distance_inputs(models, method: str, device=None) -> ModelInputs:
+    """`models` resolved for _distances(method). Under "wide" up to 128 models; past 32 of them an
+    fp64 dtype group raises ValueError before anything is copied or launched (the Gram kernels take
+    no fp64 and the exact kernel stops at 32)."""
+    if method != "wide":
+        return ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance", device)
+    n = len(models)
+    _native.check_gramwide_fan_in(n)
+    if n > _native.MAX_PAIRDIST_INPUTS and any(p.dtype == torch.float64 and p.numel() for p in module_params(models[0])):
+        raise ValueError(f"the wide Gram distance takes no fp64 parameters (products of fp64 values are not exact "
+                         f"in double), and the exact kernel that serves them takes at most "
+                         f"{_native.MAX_PAIRDIST_INPUTS} models (got {n})")
+    return ModelInputs(models, _native.MAX_GRAMWIDE_INPUTS, "wide Gram distance", device)
+
+
 def _distances(inputs: ModelInputs, method: str = "exact") -> torch.Tensor:
     n, dev, layout = inputs.n, inputs.dev, inputs.layout
+    flat = {"exact": _native.pairwise_sqdist, "gram": _native.gram_sqdist, "wide": _native.gram_sqdist_wide}
+    tensors = {"exact": _native.pairwise_sqdist_tensors_raw, "gram": _native.gram_sqdist_tensors_raw,
+               "wide": _native.gram_sqdist_wide_tensors_raw}
     with torch.no_grad(), torch.cuda.device(dev):
         raw_stream = torch._C._cuda_getCurrentRawStream(dev.index)
         d2 = torch.empty(n * n, dtype=torch.float64, device=dev)
         first = True
         for dt, kind, data in inputs:
-            # the Gram kernel takes no fp64 (its products would not be exact): such a group stays exact
-            gram = method == "gram" and dt != torch.float64
+            # the Gram kernels take no fp64 (its products would not be exact): such a group stays exact
+            use = "exact" if dt == torch.float64 else method
             if kind == "flat":
-                (_native.gram_sqdist if gram else _native.pairwise_sqdist)(data, d2, accumulate=not first)
+                flat[use](data, d2, accumulate=not first)
             else:
-                tensors_raw = _native.gram_sqdist_tensors_raw if gram else _native.pairwise_sqdist_tensors_raw
-                tensors_raw([p for ptrs in data for p in ptrs], n, layout.split_sizes[dt],
-                            _native.dtype_code(dt, single_task=True), d2.data_ptr(), not first, raw_stream)
+                tensors[use]([p for ptrs in data for p in ptrs], n, layout.split_sizes[dt],
+                             _native.dtype_code(dt, single_task=True), d2.data_ptr(), not first, raw_stream)
             first = False
         if first:
             d2.zero_()
@@ -329,10 +360,14 @@ def model_distances(models: List[nn.Module], device=None, method: str = "exact")
     (S_i + S_j) of the exact one per group, S_i the squared distance of model i
     to models[0], and NaN when model i or j holds a NaN or infinite parameter
     (where the exact entry tells NaN from +Inf). An fp64 group goes through the
-    exact kernel under either method, accumulating into the same matrix. Any
-    other string raises ValueError."""
+    exact kernel under either method, accumulating into the same matrix.
+
+    method "wide" is "gram" for up to 128 models (dlsim_gram_sqdist_wide,
+    DESIGN.md §8v: the same contract and bound, and the same bits as "gram" up
+    to 32 models). Past 32 models an fp64 group raises ValueError before
+    anything is launched. Any other string raises ValueError."""
     check_distance_method(method)
-    return _distances(ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance", device), method)
+    return _distances(_distance_inputs(models, method, device), method)
 
 
 def distances_arena_tasks(prepared: List[ArenaTask]) -> List[torch.Tensor]:
@@ -744,14 +779,15 @@ def krum_modules(models: List[nn.Module], f: int, m: Optional[int], to_host: Opt
     to_host says otherwise.
 
     The selection needs the matrix on the host: one D2H copy of n*n doubles
-    and one stream synchronisation per call. distance: model_distances' method."""
+    and one stream synchronisation per call. distance: model_distances' method
+    ("wide": up to 128 models; Multi-Krum's reduce takes as many)."""
     from dasklearn_amd.gradient_aggregation import krum as _krum
     model0 = models[0]  # IndexError for an empty list, as FedAvg
     n = len(models)
-    _native.check_pairdist_fan_in(n)
+    _check_distance_fan_in(n, distance)
     _krum.check_krum_params(n, f, 1 if m is None else m)
     check_distance_method(distance)
-    inputs = ModelInputs(models, _native.MAX_PAIRDIST_INPUTS, "pairwise-distance")
+    inputs = _distance_inputs(models, distance)
     chosen = _krum.krum_select(_distances(inputs, distance).tolist(), f, 1 if m is None else m)
     host_out = inputs.host_out(to_host)
     if m is None:

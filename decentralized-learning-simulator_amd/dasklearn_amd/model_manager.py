@@ -22,7 +22,7 @@ closest to the median; MULTI_KRUM with `settings.aggregation_krum_rule =
 `aggregation_byzantine` (`aggregation_multi_krum_m` must then be None). Any
 other string raises ValueError. KRUM and MULTI_KRUM (both of its rules) take
 their distance matrix from the kernel `settings.aggregation_distance` names:
-"exact" (the default) or "gram" (krum.py; any other string raises ValueError). The
+"exact" (the default), "gram" or "wide" (krum.py; any other string raises ValueError). The
 `dataset` argument is accepted and ignored, as the reference's aggregate task
 passes None (functions.py:99).
 """
@@ -57,8 +57,8 @@ def krum_rule_name(settings) -> str:
 
 
 def distance_name(settings) -> str:
-    """"exact" (the default) or "gram": the distance kernel of KRUM and MULTI_KRUM."""
-    return _rule(settings, "aggregation_distance", ("exact", "gram"))
+    """"exact" (the default), "gram" or "wide" (up to 128 models): the distance kernel of KRUM and MULTI_KRUM."""
+    return _rule(settings, "aggregation_distance", ("exact", "gram", "wide"))
 
 
 class ModelManager:

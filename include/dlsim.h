@@ -906,6 +906,44 @@ int dlsim_gram_sqdist_tensors(const void* const* d_inputs, int n, int t, const s
 int dlsim_gramdist_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
 
 /*
+ * dlsim_gram_sqdist_wide: dlsim_gram_sqdist for up to 128 inputs (DESIGN.md
+ * 8v): the distance matrix of a server round's 50 to 100 sampled clients in
+ * one call that reads every row once. The contract, the accuracy bound (which
+ * depends on n_elems, not on n), the dtypes (DLSIM_F64 is DLSIM_E_DTYPE, decided
+ * before n is looked at), the arguments, n == 1, n_elems == 0, the overlap
+ * rules and the argument errors are dlsim_gram_sqdist's, with
+ *   n       1 <= n <= DLSIM_MAX_GRAMWIDE_INPUTS
+ * n <= 32 is forwarded to dlsim_gram_sqdist's kernel: the same bits. For
+ * 33 <= n <= 128 a block of four waves centres every element once into LDS
+ * and its waves multiply disjoint 16 x 16 block products out of it; the rows
+ * are centred on row 0 as a whole, which a matrix assembled from 32-row
+ * dlsim_gram_sqdist calls would not be. No atomics: two calls with the same
+ * (n, dtype, n_elems, alignment class) return the same bits. Stream-ordered.
+ * (New: no reference counterpart.)
+ */
+#define DLSIM_MAX_GRAMWIDE_INPUTS 128
+int dlsim_gram_sqdist_wide(const void* const* d_inputs, int n, size_t n_elems, int dtype, double* d_d2, int accumulate,
+                           void* stream);
+
+/*
+ * dlsim_gram_sqdist_wide_tensors: dlsim_gram_sqdist_wide over t separate
+ * tensors per model, as dlsim_gram_sqdist_tensors: bit-identical to t flat
+ * calls in order, the first with the caller's `accumulate` and the rest with
+ * 1. (New: no reference counterpart.)
+ */
+int dlsim_gram_sqdist_wide_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems, int dtype,
+                                   double* d_d2, int accumulate, void* stream);
+
+/*
+ * dlsim_gramwide_geometry: the tile and the grid dlsim_gram_sqdist_wide uses
+ * for n inputs of n_elems elements, dealt as dlsim_pairdist_geometry
+ * describes: dlsim_gramdist_geometry's for n <= 32, above it tiles of 64
+ * elements in either alignment class. Host only. (New: no reference
+ * counterpart.)
+ */
+int dlsim_gramwide_geometry(int n, int dtype, size_t n_elems, size_t* tile_elems, unsigned* blocks);
+
+/*
  * dlsim_pairwise_sqdist_batched: b independent dlsim_pairwise_sqdist_tensors
  * tasks in a few launches (the Krum or Multi-Krum distance matrices, or the
  * consensus distances, of one simulated round's peers). The

@@ -41,8 +41,20 @@ rows (for DESIGN.md §8k).
            Krum and one Bulyan aggregate of 17 and of 32 ResNet-18-shaped
            device-arena models with distance "exact" and "gram".
 
+  wide     (--wide, instead of the above) dlsim_gram_sqdist_wide
+           on n = 33, 64, 100 and 128 fp32 rows of 11,181,642 elements and on
+           n = 64 bf16 rows of 125,000,000, between two runs of yardstick (a),
+           the exact weighted reduce over the same n rows (the cost of reading
+           them once), and beside yardstick (b), the dlsim_gram_sqdist calls
+           over every pair of 16-row groups that would assemble the matrix
+           without this kernel (legs yard_1, groups, wide, yard_2; the same
+           windows, rotation and decoy rule); then (c) Krum and Multi-Krum with
+           distance "wide" over 64 and 100 ResNet-18-shaped device-arena models
+           next to FedAvg on the same models.
+
     python scripts/bench_krum.py [--windows 5] [--launches 200] [--skip-bf16] [--out FILE]
     python scripts/bench_krum.py --gram [--windows 5] [--launches 200] [--skip-bf16] [--out FILE]
+    python scripts/bench_krum.py --wide [--windows 5] [--launches 50] [--skip-bf16] [--out FILE]
     python scripts/bench_krum.py --batch [--windows 7] [--launches N] [--legs abcd] [--out FILE]
 One JSON line per measurement (also written to --out). --launches is the number
 of whole calls per window of legs (a), (c) and (d): 20 in (a), where a call is
@@ -167,7 +179,68 @@ def kernel_lines(P, tdt, n, launches, nwin, gram=False):
               yard_spread=round(abs(res["yard_1"] - res["yard_2"]) / yard_us, 4), **extra))
 
 
-def plugin_lines(reps=20, gram=False):
+class GroupPairs:
+    """The only HIP route to a matrix over n > 32 rows before dlsim_gram_sqdist_wide: one
+    dlsim_gram_sqdist call per pair of 16-row groups (each centred on its own first row)."""
+
+    def __init__(self, inputs, d2):
+        groups = [inputs[k:k + 16] for k in range(0, len(inputs), 16)]
+        self.calls = [DistPlan(groups[a] + groups[b], d2[:(len(groups[a]) + len(groups[b])) ** 2], "dlsim_gram_sqdist")
+                      for a in range(len(groups)) for b in range(a + 1, len(groups))]
+
+    def launch(self, stream=None):
+        for c in self.calls:
+            c.launch(stream)
+
+
+def wide_lines(P, tdt, n, launches, nwin):
+    dev = torch.device("cuda", 0)
+    esz = torch.empty((), dtype=tdt).element_size()
+    byts = n * P * esz
+    sets = max(3, -(-(1 << 30) // byts))
+    out_sets = -(-max(sets, -(-(1 << 30) // (P * esz))) // sets) * sets
+    stride = row_stride(P, esz)
+    # + 1: the decoy set, read first and never timed (DESIGN.md §5f)
+    rows = aligned_empty((sets + 1) * n * stride, tdt, dev, base_align(P * esz, esz)).view(sets + 1, n, stride)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for s in range(sets + 1):
+        for i in range(n):
+            rows[s, i, :P].copy_((torch.randn(P, generator=g, device=dev) * 0.05).to(tdt))
+    outs = [arena_empty(P, tdt, dev) for _ in range(out_sets + 1)]
+    d2s = [torch.empty(n * n, dtype=torch.float64, device=dev) for _ in range(sets + 1)]
+    w = np.full(n, 1.0 / n, dtype=np.float32)
+    ins = [[rows[s, i, :P] for i in range(n)] for s in range(sets + 1)]
+    decoy = DistPlan(ins[sets], d2s[sets], "dlsim_gram_sqdist_wide")
+    for _ in range(4):
+        decoy.launch()
+    torch.cuda.synchronize()
+    tile, blocks = _native.gramwide_geometry(n, tdt, P)
+    base = {"params": P, "dtype": str(tdt).replace("torch.", ""), "n": n, "bytes": byts, "rotating_sets": sets,
+            "launches_per_window": launches, "windows": nwin}
+    res = {}
+    for key in ("yard_1", "groups", "wide", "yard_2"):
+        if key == "wide":
+            plans = [DistPlan(ins[j], d2s[j], "dlsim_gram_sqdist_wide") for j in range(sets)]
+        elif key == "groups":
+            plans = [GroupPairs(ins[j], d2s[j]) for j in range(sets)]
+        else:
+            plans = [_native.ReducePlan(ins[j % sets], w, outs[j], _native.DLSIM_EXACT) for j in range(out_sets)]
+        ws = windows(plans, launches, nwin)
+        res[key] = ws[len(ws) // 2]
+        line = dict(base, leg=key, median_us=round(ws[len(ws) // 2], 3), min_us=round(ws[0], 3), max_us=round(ws[-1], 3))
+        if key == "wide":
+            line.update(kernel="dlsim::k_gramwide + dlsim::k_gramwide_finish", tile_elems=tile, blocks=blocks,
+                        GBps=round(byts / res[key] / 1e3, 1))
+        if key == "groups":
+            line.update(calls=len(plans[0].calls))
+        emit(line)
+    yard_us = (res["yard_1"] + res["yard_2"]) / 2
+    emit(dict(base, leg="ratio", wide_over_yard=round(res["wide"] / yard_us, 4),
+              wide_over_groups=round(res["wide"] / res["groups"], 4),
+              yard_spread=round(abs(res["yard_1"] - res["yard_2"]) / yard_us, 4)))
+
+
+def plugin_lines(reps=20, gram=False, wide=False):
     sys.path.insert(0, ROOT)
     from bench import resnet18_shapes
     dev = torch.device("cuda", 0)
@@ -185,6 +258,10 @@ def plugin_lines(reps=20, gram=False):
         cases = [(n, tuple((f"{cls.__name__}(f={f}, {d})", cls.with_params(f, distance=d))
                            for cls in (Krum, Bulyan) for d in ("exact", "gram", "exact")))
                  for n, f in ((17, 3), (32, 7))]
+    if wide:  # Krum and Multi-Krum over a server round's clients, FedAvg before and after
+        cases = [(n, (("FedAvg", FedAvg), (f"Krum(f={f}, wide)", Krum.with_params(f, distance="wide")),
+                      (f"MultiKrum(f={f}, wide)", MultiKrum.with_params(f, distance="wide")), ("FedAvg_again", FedAvg)))
+                 for n, f in ((64, 15), (100, 24))]
     for n, aggs in cases:
         models = [arena.to_device_arena(Shaped(100 + i), dev) for i in range(n)]
         plugin_case_lines(models, aggs, reps, shapes)
@@ -392,6 +469,8 @@ def main():
     ap.add_argument("--batch", action="store_true", help="the batched entry's legs (a)-(d) instead of the flat kernel's")
     ap.add_argument("--legs", default="abcd", help="with --batch: which of the legs a, b, c, d")
     ap.add_argument("--gram", action="store_true", help="dlsim_gram_sqdist beside the exact kernel and the yardstick")
+    ap.add_argument("--wide", action="store_true",
+                    help="dlsim_gram_sqdist_wide over 33 to 128 rows beside its two yardsticks")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -402,6 +481,16 @@ def main():
              "c": lambda: batch_leg_c(a.windows, a.launches or 200),
              "d": lambda: batch_leg_c(a.windows, a.launches or 200, b=2, case="d")}[leg]()
             torch.cuda.empty_cache()
+        write_out(a.out)
+        return
+    if a.wide:
+        for n in (33, 64, 100, 128):
+            wide_lines(11_181_642, torch.float32, n, a.launches or 50, a.windows)
+            torch.cuda.empty_cache()
+        if not a.skip_bf16:
+            wide_lines(125_000_000, torch.bfloat16, 64, a.launches or 50, a.windows)
+            torch.cuda.empty_cache()
+        plugin_lines(reps=10, wide=True)
         write_out(a.out)
         return
     a.launches = a.launches or 200
