@@ -315,6 +315,10 @@ hipError_t robust_flat(const void* const* in, int n, int lo, int hi, void* out, 
 hipError_t robust_batched(int b, const int* fan_in, const void* const* in, const int* lo, const int* hi,
                           void* const* outs, const size_t* nelem, int dtype, hipStream_t st);
 size_t robust_batch_tile_elems(int n, int dtype);
+// its wide form, n <= 128 (inst_robust_wide.hip)
+hipError_t robust_wide_flat(const void* const* in, int n, int lo, int hi, void* out, size_t nelem, int dtype,
+                            hipStream_t st);
+void robust_wide_geometry(int n, int dtype, size_t* tile_elems, int* lanes_per_elem);
 hipError_t robust_nearest_flat(const void* const* in, int n, int keep, void* out, size_t nelem, int dtype,
                                hipStream_t st);
 hipError_t pairdist_flat(const void* const* in, int n, size_t nelem, int dtype, double* d2, int accumulate,
@@ -368,6 +372,7 @@ void mx_batch_limits(int* max_tasks, int* max_slots);
 
 // why each family stops at its DLSIM_MAX_*_INPUTS (check_fan_in, fanin_checks.hpp)
 constexpr const char* kRobustLimit = "the sorting network is held in registers";
+constexpr const char* kRobustWideLimit = "four lanes of a wave hold 32 keys each";
 constexpr const char* kPairdistLimit = "the pairs' accumulators are held in registers";
 constexpr const char* kGramdistLimit = "two row blocks of the 16 x 16 matrix instruction";
 constexpr const char* kGramwideLimit = "eight row blocks of the 16 x 16 matrix instruction";
@@ -1296,6 +1301,54 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
         robust_flat(row, n, lo, hi, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
     if (e != hipSuccess) return hip_fail(e, "robust reduce launch");
   }
+  return DLSIM_OK;
+}
+
+int dlsim_robust_reduce_wide(const void* const* d_inputs, int n, int lo, int hi, void* d_out, size_t n_elems, int dtype,
+                             void* stream) {
+  g_err.clear();
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_WIDE_INPUTS, dtype, kRobustWideLimit);
+  if (rc == DLSIM_OK) rc = check_robust_window(n, lo, hi);
+  if (rc != DLSIM_OK) return rc;
+  if (!d_inputs) return fail(DLSIM_E_ARG, "null inputs array");
+  if (n_elems == 0) return DLSIM_OK;
+  if (!d_out) return fail(DLSIM_E_ARG, "null output pointer");
+  const size_t bytes = n_elems * elem_bytes(dtype);  // any shared byte is rejected, as dlsim_robust_reduce
+  rc = check_inputs_apart(d_inputs, 1, n, bytes, addr(d_out), addr(d_out) + bytes, "output");
+  if (rc != DLSIM_OK) return rc;
+  const hipError_t e = robust_wide_flat(d_inputs, n, lo, hi, d_out, n_elems, dtype, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? DLSIM_OK : hip_fail(e, "wide robust reduce launch");
+}
+
+int dlsim_robust_reduce_wide_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                     const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype,
+                                     void* stream) {
+  g_err.clear();
+  if (t < 0) return fail(DLSIM_E_ARG, "t must be >= 0 (got %d)", t);
+  int rc = check_fan_in(n, DLSIM_MAX_ROBUST_WIDE_INPUTS, dtype, kRobustWideLimit);
+  if (rc == DLSIM_OK) rc = check_robust_window(n, lo, hi);
+  if (rc != DLSIM_OK || t == 0) return rc;
+  if (!d_inputs || !n_elems || !out_off_bytes) return fail(DLSIM_E_ARG, "null array argument");
+  rc = check_tensor_outputs(d_inputs, n, t, n_elems, d_out, out_off_bytes, elem_bytes(dtype));
+  if (rc != DLSIM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const void* row[DLSIM_MAX_ROBUST_WIDE_INPUTS];
+  for (int k = 0; k < t; ++k) {
+    if (n_elems[k] == 0) continue;
+    gather_row(d_inputs, n, t, k, row);
+    const hipError_t e =
+        robust_wide_flat(row, n, lo, hi, static_cast<char*>(d_out) + out_off_bytes[k], n_elems[k], dtype, st);
+    if (e != hipSuccess) return hip_fail(e, "wide robust reduce launch");
+  }
+  return DLSIM_OK;
+}
+
+int dlsim_robust_wide_geometry(int n, int dtype, size_t* tile_elems, int* lanes_per_elem) {
+  g_err.clear();
+  const int rc = check_fan_in(n, DLSIM_MAX_ROBUST_WIDE_INPUTS, dtype, kRobustWideLimit);
+  if (rc != DLSIM_OK) return rc;
+  if (!tile_elems || !lanes_per_elem) return fail(DLSIM_E_ARG, "null result pointer");
+  robust_wide_geometry(n, dtype, tile_elems, lanes_per_elem);
   return DLSIM_OK;
 }
 

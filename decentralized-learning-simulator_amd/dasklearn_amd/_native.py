@@ -64,6 +64,9 @@ EXPORTS = (
     "dlsim_sgd_momentum_step_tensors",
     "dlsim_robust_reduce",
     "dlsim_robust_reduce_tensors",
+    "dlsim_robust_reduce_wide",
+    "dlsim_robust_reduce_wide_tensors",
+    "dlsim_robust_wide_geometry",
     "dlsim_robust_reduce_batched",
     "dlsim_robust_batch_geometry",
     "dlsim_robust_reduce_tensors_batched",
@@ -268,6 +271,12 @@ def load() -> ctypes.CDLL:
         lib.dlsim_robust_reduce_tensors.argtypes = [ctypes.POINTER(vp), i, i, ctypes.POINTER(sz), ctypes.POINTER(sz),
                                                     i, i, vp, i, vp]
         lib.dlsim_robust_reduce_tensors.restype = i
+        lib.dlsim_robust_reduce_wide.argtypes = lib.dlsim_robust_reduce.argtypes
+        lib.dlsim_robust_reduce_wide.restype = i
+        lib.dlsim_robust_reduce_wide_tensors.argtypes = lib.dlsim_robust_reduce_tensors.argtypes
+        lib.dlsim_robust_reduce_wide_tensors.restype = i
+        lib.dlsim_robust_wide_geometry.argtypes = [i, i, ctypes.POINTER(sz), ctypes.POINTER(i)]
+        lib.dlsim_robust_wide_geometry.restype = i
         lib.dlsim_robust_reduce_batched.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(vp), ctypes.POINTER(i),
                                                     ctypes.POINTER(i), ctypes.POINTER(vp), ctypes.POINTER(sz), i, vp]
         lib.dlsim_robust_reduce_batched.restype = i
@@ -630,6 +639,7 @@ MAX_ROBUST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_ROBUST_INPUTS
 MAX_PAIRDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_PAIRDIST_INPUTS
 MAX_REDUCEDIST_INPUTS = 32  # include/dlsim.h DLSIM_MAX_REDUCEDIST_INPUTS
 MAX_GRAMWIDE_INPUTS = 128  # include/dlsim.h DLSIM_MAX_GRAMWIDE_INPUTS
+MAX_ROBUST_WIDE_INPUTS = 128  # include/dlsim.h DLSIM_MAX_ROBUST_WIDE_INPUTS
 
 
 def _check_fan_in(n: int, limit: int, message: str) -> None:
@@ -641,6 +651,11 @@ def _check_fan_in(n: int, limit: int, message: str) -> None:
 def check_robust_fan_in(n: int) -> None:
     _check_fan_in(n, MAX_ROBUST_INPUTS, "the median and trimmed-mean kernels take at most {limit} models (got {n}): "
                                         "the sorting network is held in registers")
+
+
+def check_robust_wide_fan_in(n: int) -> None:
+    _check_fan_in(n, MAX_ROBUST_WIDE_INPUTS, "the wide median and trimmed-mean kernels take at most {limit} models "
+                                             "(got {n}): four lanes of a wave hold 32 keys each")
 
 
 def check_pairdist_fan_in(n: int) -> None:
@@ -720,6 +735,43 @@ def robust_reduce_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[i
            load().dlsim_robust_reduce_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
                                               _size_array(out_offsets), int(lo), int(hi), out_base, dtype,
                                               stream_handle))
+
+
+def robust_reduce_wide(inputs, lo: int, hi: int, out, stream=None):
+    """dlsim_robust_reduce_wide: robust_reduce for up to 128 inputs, the same
+    contract and bits (n <= 32 runs robust_reduce's kernels). Tensors,
+    exceptions and stream order as robust_reduce."""
+    n = len(inputs)
+    if n < 1:
+        raise IndexError("list index out of range")
+    check_robust_wide_fan_in(n)
+    dt, numel = _check_flat_inputs(inputs, out, out.device, "robust reduce")
+    _check("dlsim_robust_reduce_wide",
+           load().dlsim_robust_reduce_wide(_ptr_array([t.data_ptr() for t in inputs]), n, int(lo), int(hi),
+                                           out.data_ptr(), numel, dtype_code(dt, single_task=True),
+                                           _stream_handle(out.device, stream)))
+    return out
+
+
+def robust_reduce_wide_tensors_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int], out_offsets: Sequence[int],
+                                   lo: int, hi: int, out_base: int, dtype: int, stream_handle) -> None:
+    """dlsim_robust_reduce_wide_tensors, as robust_reduce_tensors_raw."""
+    check_robust_wide_fan_in(n)
+    _check("dlsim_robust_reduce_wide_tensors",
+           load().dlsim_robust_reduce_wide_tensors(_ptr_array(in_ptrs), n, len(numels), _size_array(numels),
+                                                   _size_array(out_offsets), int(lo), int(hi), out_base, dtype,
+                                                   stream_handle))
+
+
+def robust_wide_geometry(n: int, torch_dtype):
+    """(tile elements, lanes per element) of dlsim_robust_reduce_wide for n
+    inputs (dlsim_robust_wide_geometry; no GPU needed): 1 lane for n <= 32,
+    2 for n <= 64, 4 for n <= 128."""
+    tile, lanes = ctypes.c_size_t(0), ctypes.c_int(0)
+    _check("dlsim_robust_wide_geometry",
+           load().dlsim_robust_wide_geometry(int(n), dtype_code(torch_dtype, single_task=True), ctypes.byref(tile),
+                                             ctypes.byref(lanes)))
+    return tile.value, lanes.value
 
 
 def robust_reduce_tensors_batched_raw(in_ptrs: Sequence[int], n: int, numels: Sequence[int],

@@ -41,10 +41,15 @@ def method_window(method, settings):
     TRIMMED_MEAN with settings.aggregation_trim (default 1, as ModelManager);
     None for every other method, and for TRIMMED_MEAN under
     settings.aggregation_trim_rule = "median" (MeanAroundMedian has no window
-    per launch and no batched form: it runs as a plugin, per task)."""
+    per launch and no batched form: it runs as a plugin, per task), and for
+    both methods under settings.aggregation_sort = "wide" (the wide kernels
+    have no batched form either: the plugin runs per task, so both
+    dispatchers agree with functions.aggregate by construction)."""
     from .gradient_aggregation import GradientAggregationMethod as M
     from .gradient_aggregation.robust import median_window, trimmed_window
-    from .model_manager import trim_rule
+    from .model_manager import sort_name, trim_rule
+    if method in (M.MEDIAN, M.TRIMMED_MEAN) and sort_name(settings) != "register":
+        return None
     if method == M.MEDIAN:
         return median_window
     if method == M.TRIMMED_MEAN:

@@ -18,11 +18,16 @@ copy.deepcopy(models[0])'s, as in FedAvg. Inputs are only read.
 Both are unweighted: `weights` of None or [] is accepted; a non-empty list of
 another length than the models raises AssertionError (as FedAvg), one of the
 right length ValueError. An empty model list raises IndexError; more than 32
-models, or a model whose parameter list differs from models[0]'s, ValueError.
+models (128 under sort="wide"), or a model whose parameter list differs from
+models[0]'s, ValueError.
 
 The arithmetic runs in one HIP kernel per dtype group
 (csrc/robust_kernels.hpp: an in-register sorting network per element) through
-dasklearn_amd.model_inputs.robust_modules.
+dasklearn_amd.model_inputs.robust_modules. sort="wide"
+(`settings.aggregation_sort`, CoordinateMedian.with_sort, TrimmedMean.with_trim)
+takes 33 to 128 models through csrc/robust_wide_kernels.hpp, where two or four
+lanes of a wave share an element's values; up to 32 models it
+gives the default's bits.
 
 MeanAroundMedian (MeaMed / Phocas, Xie et al., 2018; a variant of TRIMMED_MEAN:
 `settings.aggregation_trim_rule = "median"`) averages, per element, the `keep`
@@ -35,7 +40,7 @@ from typing import List, Optional
 from torch import nn
 
 from dasklearn_amd.gradient_aggregation import GradientAggregation
-from dasklearn_amd.model_inputs import nearest_modules, robust_modules
+from dasklearn_amd.model_inputs import check_robust_sort, nearest_modules, robust_modules
 
 
 def _check_unweighted(name: str, models, weights) -> None:
@@ -69,13 +74,23 @@ class CoordinateMedian(GradientAggregation):
     minority of peers is never selected; the result is NaN only where at
     least n - (n-1)//2 of the n values are NaN."""
 
-    @staticmethod
-    def aggregate(models: List[nn.Module], weights: Optional[List[float]] = None,
-                  to_host: Optional[bool] = None) -> nn.Module:
+    sort = "register"
+
+    @classmethod
+    def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
+                  to_host: Optional[bool] = None, sort: Optional[str] = None) -> nn.Module:
         """to_host=None (default): the result lives where models[0] lives;
-        False keeps it on the GPU."""
+        False keeps it on the GPU. sort: "register" (at most 32 models) or
+        "wide" (at most 128); None is the class's."""
         _check_unweighted("CoordinateMedian", models, weights)
-        return robust_modules(models, median_window, to_host=to_host)
+        return robust_modules(models, median_window, to_host=to_host, sort=cls.sort if sort is None else sort)
+
+    @classmethod
+    def with_sort(cls, sort: str):
+        """A CoordinateMedian class whose aggregate(models, weights=None,
+        to_host=None) sorts with `sort`: the plugin signature ModelManager
+        calls."""
+        return type(f"CoordinateMedian_{check_robust_sort(sort)}", (cls,), {"sort": sort})
 
 
 class TrimmedMean(GradientAggregation):
@@ -86,23 +101,28 @@ class TrimmedMean(GradientAggregation):
     sending Inf or NaN leave the result finite."""
 
     trim = 1
+    sort = "register"
 
     @classmethod
     def aggregate(cls, models: List[nn.Module], weights: Optional[List[float]] = None,
-                  to_host: Optional[bool] = None, trim: Optional[int] = None) -> nn.Module:
+                  to_host: Optional[bool] = None, trim: Optional[int] = None, sort: Optional[str] = None) -> nn.Module:
+        """sort: "register" (at most 32 models) or "wide" (at most 128); None
+        is the class's."""
         _check_unweighted("TrimmedMean", models, weights)
         b = cls.trim if trim is None else trim
-        return robust_modules(models, lambda n: trimmed_window(n, b), to_host=to_host)
+        return robust_modules(models, lambda n: trimmed_window(n, b), to_host=to_host,
+                              sort=cls.sort if sort is None else sort)
 
     @classmethod
-    def with_trim(cls, trim: int):
+    def with_trim(cls, trim: int, sort: str = "register"):
         """A TrimmedMean class whose aggregate(models, weights=None,
-        to_host=None) trims `trim` values at each end: the plugin signature
-        ModelManager calls."""
+        to_host=None) trims `trim` values at each end and sorts with `sort`:
+        the plugin signature ModelManager calls."""
         trim = int(trim)
         if trim < 0:
             raise ValueError(f"trim must be >= 0 (got {trim})")
-        return type(f"TrimmedMean{trim}", (cls,), {"trim": trim})
+        name = f"TrimmedMean{trim}" if check_robust_sort(sort) == "register" else f"TrimmedMean{trim}_{sort}"
+        return type(name, (cls,), {"trim": trim, "sort": sort})
 
 
 class MeanAroundMedian(GradientAggregation):

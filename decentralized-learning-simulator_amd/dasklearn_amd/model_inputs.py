@@ -130,7 +130,18 @@ def flat_groups(inputs: ModelInputs) -> Dict[torch.dtype, torch.Tensor]:
     return flats
 
 
-def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Optional[bool] = None) -> nn.Module:
+ROBUST_SORTS = ("register", "wide")
+
+
+def check_robust_sort(sort: str) -> str:
+    """ValueError unless `sort` is one of ROBUST_SORTS."""
+    if sort not in ROBUST_SORTS:
+        raise ValueError(f"the sort must be one of {', '.join(repr(m) for m in ROBUST_SORTS)} (got {sort!r})")
+    return sort
+
+
+def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Optional[bool] = None,
+                   sort: str = "register") -> nn.Module:
     """The coordinate-wise order-statistic aggregate of `models` on the GPU
     (dlsim_robust_reduce): per parameter element the n models' values are
     sorted and the window [lo, hi) = lo_hi_fn(n) of them is averaged. As
@@ -138,12 +149,23 @@ def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Opti
     (buffers and attributes are models[0]'s), the models only read, one launch
     per dtype group, the result where models[0] lives unless to_host says
     otherwise. A model whose parameter list differs from models[0]'s raises
-    ValueError (no zip semantics here); more than 32 models too."""
+    ValueError (no zip semantics here); more than 32 models too. sort "wide"
+    (dlsim_robust_reduce_wide) takes up to 128 models: past 32
+    the values are sorted across two or four lanes of a wave; up to 32 it runs
+    the same kernels and gives the same bits. Its tensors read in place take one
+    launch each."""
     models[0]  # IndexError for an empty list, as FedAvg
     n = len(models)
-    _native.check_robust_fan_in(n)
+    wide = check_robust_sort(sort) == "wide"
+    if wide:
+        _native.check_robust_wide_fan_in(n)
+    else:
+        _native.check_robust_fan_in(n)
     lo, hi = lo_hi_fn(n)
-    inputs = ModelInputs(models, _native.MAX_ROBUST_INPUTS, "median and trimmed-mean", device)
+    if wide:
+        inputs = ModelInputs(models, _native.MAX_ROBUST_WIDE_INPUTS, "wide median and trimmed-mean", device)
+    else:
+        inputs = ModelInputs(models, _native.MAX_ROBUST_INPUTS, "median and trimmed-mean", device)
     layout, dev, host_out = inputs.layout, inputs.dev, inputs.host_out(to_host)
     outs: Dict[torch.dtype, torch.Tensor] = {dt: torch.empty(0, dtype=dt, device="cpu" if host_out else dev)
                                              for dt in layout.groups if not layout.totals[dt]}
@@ -152,7 +174,12 @@ def robust_modules(models: List[nn.Module], lo_hi_fn, device=None, to_host: Opti
         for dt, kind, data in inputs:
             out = outs[dt] = arena_empty(layout.totals[dt], dt, dev)
             if kind == "flat":
-                _native.robust_reduce(data, lo, hi, out)
+                (_native.robust_reduce_wide if wide else _native.robust_reduce)(data, lo, hi, out)
+            elif wide:
+                _native.robust_reduce_wide_tensors_raw([p for ptrs in data for p in ptrs], n,
+                                                       layout.split_sizes[dt], layout.byte_offsets[dt], lo, hi,
+                                                       out.data_ptr(), _native.dtype_code(dt, single_task=True),
+                                                       raw_stream)
             else:
                 # every tensor a sub-task of one batched dispatch, not a launch of its own
                 _native.robust_reduce_tensors_batched_raw([p for ptrs in data for p in ptrs], n,

@@ -22,7 +22,11 @@ closest to the median; MULTI_KRUM with `settings.aggregation_krum_rule =
 `aggregation_byzantine` (`aggregation_multi_krum_m` must then be None). Any
 other string raises ValueError. KRUM and MULTI_KRUM (both of its rules) take
 their distance matrix from the kernel `settings.aggregation_distance` names:
-"exact" (the default), "gram" or "wide" (krum.py; any other string raises ValueError). The
+"exact" (the default), "gram" or "wide" (krum.py; any other string raises ValueError).
+MEDIAN and TRIMMED_MEAN under the "rank" rule sort with the kernels
+`settings.aggregation_sort` names: "register" (the default, at most 32 models)
+or "wide" (at most 128, robust.py); "wide" with the "median" trim rule raises
+ValueError, as the mean around the median stops at 32 models. The
 `dataset` argument is accepted and ignored, as the reference's aggregate task
 passes None (functions.py:99).
 """
@@ -61,6 +65,11 @@ def distance_name(settings) -> str:
     return _rule(settings, "aggregation_distance", ("exact", "gram", "wide"))
 
 
+def sort_name(settings) -> str:
+    """"register" (the default, at most 32 models) or "wide" (at most 128): the sort of MEDIAN and TRIMMED_MEAN."""
+    return _rule(settings, "aggregation_sort", ("register", "wide"))
+
+
 class ModelManager:
 
     def __init__(self, dataset, settings, participant_index: int):
@@ -82,12 +91,17 @@ class ModelManager:
         if method == GradientAggregationMethod.FEDAVG:
             return FedAvg
         if method == GradientAggregationMethod.MEDIAN:
-            return CoordinateMedian
+            sort = sort_name(self.settings)
+            return CoordinateMedian if sort == "register" else CoordinateMedian.with_sort(sort)
         if method == GradientAggregationMethod.TRIMMED_MEAN:
             trim = getattr(self.settings, "aggregation_trim", 1)
+            sort = sort_name(self.settings)
             if trim_rule(self.settings) == "median":
+                if sort != "register":
+                    raise ValueError(f"aggregation_sort = {sort!r} serves aggregation_trim_rule = 'rank' alone: the "
+                                     f"mean around the median (aggregation_trim_rule = 'median') has no wide kernel")
                 return MeanAroundMedian.with_trim(trim)
-            return TrimmedMean.with_trim(trim)
+            return TrimmedMean.with_trim(trim, sort=sort)
         if method == GradientAggregationMethod.KRUM:
             return Krum.with_params(getattr(self.settings, "aggregation_byzantine", 1),
                                     distance=distance_name(self.settings))

@@ -694,6 +694,42 @@ int dlsim_robust_reduce_tensors(const void* const* d_inputs, int n, int t, const
                                 const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype, void* stream);
 
 /*
+ * dlsim_robust_reduce_wide: dlsim_robust_reduce for up to 128 inputs (DESIGN.md
+ * 8w): the coordinate median or trimmed mean of a server round's 50 to 100
+ * sampled clients. The contract (total order, summation order, one division,
+ * one rounding, canonical NaN), the arguments, the checks and their order, the
+ * overlap rule, n_elems == 0 and every alignment are dlsim_robust_reduce's, with
+ *   n       1 <= n <= DLSIM_MAX_ROBUST_WIDE_INPUTS
+ * n <= 32 is forwarded to dlsim_robust_reduce's kernels: the same bits. For
+ * 33 <= n <= 64 two lanes, for 65 <= n <= 128 four lanes of a wave share one
+ * element's values, 32 each, and sort them with exchanges inside and across
+ * the lanes. No allocation, no synchronisation. Stream-ordered. (New: no
+ * reference counterpart.)
+ */
+#define DLSIM_MAX_ROBUST_WIDE_INPUTS 128
+int dlsim_robust_reduce_wide(const void* const* d_inputs, int n, int lo, int hi, void* d_out, size_t n_elems, int dtype,
+                             void* stream);
+
+/*
+ * dlsim_robust_reduce_wide_tensors: dlsim_robust_reduce_wide over t separate
+ * tensors per model, with dlsim_robust_reduce_tensors's arguments and checks:
+ * one launch per non-empty tensor, bit-identical to t flat calls. (New: no
+ * reference counterpart.)
+ */
+int dlsim_robust_reduce_wide_tensors(const void* const* d_inputs, int n, int t, const size_t* n_elems,
+                                     const size_t* out_off_bytes, int lo, int hi, void* d_out, int dtype,
+                                     void* stream);
+
+/*
+ * dlsim_robust_wide_geometry: the elements of a block's tile when
+ * dlsim_robust_reduce_wide serves n 16-byte-aligned inputs of dtype, and the
+ * lanes that share one element there: 1 for n <= 32 (dlsim_robust_reduce's
+ * kernels), 2 for n <= 64, 4 for n <= 128. Block 0 takes the ragged end, blocks
+ * 1.. one tile each. Host only. (New: no reference counterpart.)
+ */
+int dlsim_robust_wide_geometry(int n, int dtype, size_t* tile_elems, int* lanes_per_elem);
+
+/*
  * dlsim_robust_reduce_batched: b independent dlsim_robust_reduce tasks in a
  * few launches (the medians or trimmed means of one simulated round's peers;
  * DESIGN.md 8m). The order-statistic counterpart of dlsim_wreduce_batched.

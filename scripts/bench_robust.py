@@ -35,9 +35,21 @@ same bytes (for DESIGN.md §8j).
            process, the yardstick before and after; fp32 at 11,181,642
            elements with n = 4, 8, 16, 32 and bf16 at 125,000,000 with n = 8.
 
+  wide     (--wide, instead of the above) dlsim_robust_reduce_wide,
+           the median and the trim-(n // 10) window, fp32 at 11,181,642 elements
+           with n = 33, 64, 100, 128 and bf16 at 125,000,000 with n = 64:
+           kernel_lines' buffers, rotation and decoy rule, every leg in this one
+           process. (a) the yardstick, dlsim_wreduce (exact) over the same rows,
+           before and after; (b) the only device route there was: the median by
+           torch.stack(rows).kthvalue, the trimmed mean by torch.stack(rows).sort(0)
+           and a mean of the window (a few launches: it is slow; skipped where
+           its temporaries would not fit beside the rotating sets); (c)
+           dlsim_robust_reduce at n = 32 on 32 of the same rows.
+
     python scripts/bench_robust.py [--windows 5] [--launches 200] [--skip-bf16]
     python scripts/bench_robust.py --batch [--windows 5] [--legs abcd]
     python scripts/bench_robust.py --nearest [--windows 5] [--launches 200] [--skip-bf16]
+    python scripts/bench_robust.py --wide [--windows 5] [--launches 50] [--skip-bf16]
 One JSON line per measurement.
 """
 from __future__ import annotations
@@ -143,6 +155,90 @@ def kernel_lines(P, tdt, n, launches, nwin):
     if "trim_1" in res:
         ratio["trim_1_over_yard"] = round(res["trim_1"] / yard_us, 4)
     print(json.dumps(ratio), flush=True)
+
+
+# ---- 33 to 128 models (--wide) ------------------------------------------------------------------
+class TorchPlan:
+    """Leg (b): what a user could run on the device before the wide kernels."""
+
+    def __init__(self, inputs, lo, hi, out):
+        self.inputs, self.lo, self.hi, self.out = list(inputs), lo, hi, out
+
+    def launch(self, stream=None):
+        x = torch.stack(self.inputs)
+        if self.hi == self.lo + 1:
+            self.out.copy_(x.kthvalue(self.lo + 1, dim=0).values)
+        else:
+            self.out.copy_(x.sort(0).values[self.lo:self.hi].float().mean(0))
+
+
+def wide_lines(P, tdt, n, launches, nwin, torch_sort=True):
+    dev = torch.device("cuda", 0)
+    esz = torch.empty((), dtype=tdt).element_size()
+    byts = (n + 1) * P * esz
+    sets = max(3, -(-(1 << 30) // (n * P * esz)))
+    out_sets = -(-max(sets, -(-(1 << 30) // (P * esz))) // sets) * sets
+    stride = row_stride(P, esz)
+    rows = aligned_empty((sets + 1) * n * stride, tdt, dev, base_align(P * esz, esz)).view(sets + 1, n, stride)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for s in range(sets + 1):
+        for i in range(n):
+            rows[s, i, :P].copy_((torch.randn(P, generator=g, device=dev) * 0.05).to(tdt))
+    outs = [arena_empty(P, tdt, dev) for _ in range(out_sets + 1)]
+    ins = [[rows[s, i, :P] for i in range(n)] for s in range(sets + 1)]
+    w = np.full(n, 1.0 / n, dtype=np.float32)
+    med, trim = ((n - 1) // 2, (n - 1) // 2 + 1), (n // 10, n - n // 10)
+    _, lanes = _native.robust_wide_geometry(n, tdt)
+
+    def wide_plan(inputs, lo, hi, out):
+        args = ((ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs]), n, lo, hi, ctypes.c_void_p(out.data_ptr()),
+                out.numel(), _native.dtype_code(out.dtype, single_task=True))
+        return Call("dlsim_robust_reduce_wide", args, out.device, (list(inputs), out))
+    decoy = wide_plan(ins[sets], *med, outs[out_sets])
+    for _ in range(8):
+        decoy.launch()
+    torch.cuda.synchronize()
+    base = {"bench": "robust_wide", "params": P, "dtype": str(tdt).replace("torch.", ""), "n": n, "lanes_per_elem": lanes,
+            "bytes": byts, "rotating_sets": sets, "rotating_outputs": out_sets, "windows": nwin}
+    legs = [("yard_1", "yard", None), ("wide_median", "wide", med), ("wide_trim", "wide", trim),
+            ("reg32_median", "reg32", (15, 16)), ("reg32_trim", "reg32", (3, 29)), ("torch_median", "torch", med)]
+    if torch_sort:
+        legs.append(("torch_trim", "torch", trim))
+    legs.append(("yard_2", "yard", None))
+    res = {}
+    for key, kind, win in legs:
+        per = launches
+        if kind == "yard":
+            plans = [_native.ReducePlan(ins[j % sets], w, outs[j], _native.DLSIM_EXACT) for j in range(out_sets)]
+        elif kind == "wide":
+            plans = [wide_plan(ins[j % sets], *win, outs[j]) for j in range(out_sets)]
+        elif kind == "reg32":
+            plans = [RobustPlan(ins[j % sets][:32], *win, outs[j]) for j in range(out_sets)]
+        else:
+            plans, per = [TorchPlan(ins[j % sets], *win, outs[j]) for j in range(min(out_sets, sets))], 2
+        try:
+            ws = windows(plans, per, nwin)
+        except RuntimeError as e:  # torch's leg alone: out of memory, or no kernel for the dtype
+            if kind != "torch":
+                raise
+            print(json.dumps(dict(base, leg=key, not_measured=str(e).splitlines()[0])), flush=True)
+            del plans
+            torch.cuda.empty_cache()
+            continue
+        b = 33 * P * esz if kind == "reg32" else byts
+        res[key] = report(base, key, ws, launches_per_window=per, GBps=round(b / ws[len(ws) // 2] / 1e3, 1),
+                          **({} if win is None else {"window": list(win)}))
+        del plans
+        torch.cuda.empty_cache()
+    yard = (res["yard_1"] + res["yard_2"]) / 2
+    line = dict(base, leg="ratio", yard_spread=round(abs(res["yard_1"] - res["yard_2"]) / yard, 4))
+    for k in ("median", "trim"):
+        line[f"wide_{k}_over_yard"] = round(res[f"wide_{k}"] / yard, 4)
+        line[f"wide_{k}_us_per_row"] = round(res[f"wide_{k}"] / n, 3)
+        line[f"reg32_{k}_us_per_row"] = round(res[f"reg32_{k}"] / 32, 3)
+        if f"torch_{k}" in res:
+            line[f"wide_{k}_over_torch"] = round(res[f"wide_{k}"] / res[f"torch_{k}"], 5)
+    print(json.dumps(line), flush=True)
 
 
 # ---- the mean around the median (--nearest) ------------------------------------------------
@@ -451,9 +547,18 @@ def main():
     ap.add_argument("--legs", default="abcd", help="with --batch: which of the legs a, b, c, d")
     ap.add_argument("--nearest", action="store_true",
                     help="dlsim_robust_nearest_reduce against dlsim_robust_reduce instead of the flat kernel's legs")
+    ap.add_argument("--wide", action="store_true",
+                    help="dlsim_robust_reduce_wide over 33 to 128 rows instead of the flat kernel's legs")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_robust.py measures on a GPU; none is visible")
+    if a.wide:
+        for n in (33, 64, 100, 128):
+            wide_lines(RESNET18_P, torch.float32, n, a.launches, a.windows)
+            torch.cuda.empty_cache()
+        if not a.skip_bf16:  # a sort of 64 x 125 M values needs 64 GB of indices: the median leg alone
+            wide_lines(125_000_000, torch.bfloat16, 64, a.launches, a.windows, torch_sort=False)
+        return
     if a.nearest:
         for n in (4, 8, 16, 32):
             nearest_lines(RESNET18_P, torch.float32, n, a.launches, a.windows)
